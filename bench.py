@@ -4,7 +4,15 @@
 One "step" = one pass of the hot path (exact search of every k-mer window + unique-to-one-group tally) over this
 rank's batch of synthetic 150-bp reads already resident in HBM; the K steps of a timed region are one job whose summed
 G + 2 counters are all-reduced over RCCL once at its end, inside the region (N > 1). Default workload = BASELINE config 2 (10 variants x 50 kb, 1M reads per GPU, k = 21, global
-mode) -> `value`. The same run also measures secondary lines (compact objects under "lines" in the JSON):
+mode) -> `value`.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times ONE region of K steps pipelined over the
+streams, scans batch 0 once more for the line's `check`, writes --dump-outputs DIR if given (dump_outputs) and prints
+the line: `value`, `ms_per_step` (the region's time / K) and `check`; `roofline`, `one_stream`, `overlap`,
+`cpu_baseline` are null and `lines` is empty. Everything else is behind --full: five regions (`value` their median), each
+also timed on one stream and with per-launch HIP events (roofline), the checks of every stream's counters, the
+instrumented twin, the LF-step and k-mer-table kernels, the PCIe-inclusive scan, the CPU baselines and the secondary
+lines (compact objects under "lines" in the JSON):
   * "local_mode": config 2 in the reference's default Phred-weighted mode (fixed_accuracy 0, arg_parse.h:23);
   * "k31": BASELINE config 3 (50 variants x 3 isolates, k = 31) at its full 10 M reads per GPU — at N = 8 the
     per-rank shard of config 4 (100 M reads over 8 GPUs, 12.5 M each);
@@ -20,8 +28,8 @@ mode) -> `value`. The same run also measures secondary lines (compact objects un
 Weak scaling: every rank scans its own shard of the deterministic read stream.
 
 stdout: ONE compact JSON line on rank 0 (< 8 KB; `compact_result`); the full per-line detail (work counters, U
-vectors, paths) goes to --detail (default profiles/r06/bench_detail_n<N>.json).
-Launch: python bench.py [--gpus N --steps K --warmup W]. N > 1 under torch.distributed.run (WORLD_SIZE must equal N),
+vectors, paths) goes to --detail (default with --full: profiles/r06/bench_detail_n<N>.json; without: not written).
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]. N > 1 under torch.distributed.run (WORLD_SIZE must equal N),
 or without a launcher: bench.py then starts torch.distributed.run over N local ranks itself (launch_plan).
 """
 from __future__ import annotations
@@ -76,9 +84,18 @@ def parse_args(argv=None):
                    help="HIP streams the timed steps alternate between (each with its own counters): consecutive "
                         "batches overlap, the next scan's workgroups taking the CUs the previous one's drain leaves "
                         "(default 2; 1 = every step on one stream, each waiting for the one before)")
-    p.add_argument("--regions", type=int, default=5,
-                   help="timed regions of K steps per line (SURVEY §8(d): the median of 5 after warm-up); each region "
-                        "times the pipelined steps, the same steps on one stream, and one stream with per-launch events")
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline: five timed regions (their median is `value`), each also "
+                        "timed on one stream and with per-launch events (roofline), the result checks, the LF-step / "
+                        "k-mer-table kernels, the PCIe-inclusive scan, the CPU baselines and the secondary lines. "
+                        "Without it: set-up, warm-up, one timed region of --steps steps, the result line")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write the counters the last timed step's scan left in its caller's "
+                        "arrays as DIR/<name>.npy (float64; see dump_outputs)")
+    p.add_argument("--regions", type=int, default=0,
+                   help="timed regions of K steps per line (0 = default: 1, or with --full 5, SURVEY §8(d): the median "
+                        "of 5 after warm-up); with --full each region times the pipelined steps, the same steps on one "
+                        "stream, and one stream with per-launch events")
     p.add_argument("--allreduce", choices=["job", "step"], default="job",
                    help="N > 1 (or --transport rccl): job = the K steps of a timed region are one job whose summed "
                         "counters are all-reduced once at its end (default; SURVEY 8(d)); step = every step's "
@@ -91,7 +108,8 @@ def parse_args(argv=None):
     p.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample duration (headline)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive host-buffer measurement")
-    p.add_argument("--detail", default="", help="full-detail JSON path (default profiles/r06/bench_detail_n<N>.json)")
+    p.add_argument("--detail", default="",
+                   help="full-detail JSON path (default: with --full profiles/r06/bench_detail_n<N>.json, else none)")
     return p.parse_args(argv)
 
 
@@ -323,6 +341,45 @@ def u_sha1(u) -> str:
     return hashlib.sha1(np.asarray(u, dtype=np.int64).tobytes()).hexdigest()[:16]
 
 
+def timed_outputs(snap, snap_job, ran, last_stream: int) -> dict:
+    """name -> float64 array: what the scans of the last timed region left in the arrays their caller handed to
+    speq_scan_reads_device, read back after the last timed step. `counts` = [T, ambiguous, U[0..G)] of the stream the
+    last step ran on (the kernel adds into them: with --allreduce job the sum of that stream's scans of the region;
+    64-bit integers, exact in float64 below 2^53), `weights` = its W[0..G) (Phred-weighted mode only), and
+    `counts_stream<i>` / `weights_stream<i>` the same of every stream that ran a step; with a communicator
+    `job_counts` / `job_weights`, the streams' sums all-reduced over the ranks."""
+    out = {}
+
+    def put(name, c):
+        out["counts" + name] = c[0].astype(np.float64)
+        if c[1] is not None:
+            out["weights" + name] = c[1].astype(np.float64)
+
+    put("", snap[last_stream])
+    for i, c in enumerate(snap):
+        if ran[i]:
+            put(f"_stream{i}", c)
+    if snap_job is not None:
+        out["job_counts"] = snap_job[0].astype(np.float64)
+        if snap_job[1] is not None:
+            out["job_weights"] = snap_job[1].astype(np.float64)
+    return out
+
+
+DUMP_LIMIT = 64 << 20  # bytes of one --dump-outputs directory
+
+
+def dump_outputs(path: str, arrays: dict) -> list:
+    """Writes every array as <path>/<name>.npy (a few KB here: G + 2 counters and G weights per stream; nothing is
+    sampled). Returns the names."""
+    if sum(v.nbytes for v in arrays.values()) > DUMP_LIMIT:
+        raise RuntimeError("--dump-outputs: the timed outputs exceed 64 MB")
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    return sorted(arrays)
+
+
 def run_workload(ctx: Ctx, cfg_no: int, k: int, n_reads: int, mode: str, steps: int, warmup: int,
                  with_lf: bool, with_pcie: bool, with_cpu: bool, cpu_seconds: float, prepared=None,
                  qual_profile: str = "q40", err: float = 0.001, cpu_extra_ports: bool = False) -> dict:
@@ -524,7 +581,10 @@ def run_workload(ctx: Ctx, cfg_no: int, k: int, n_reads: int, mode: str, steps: 
     #       (p) / (1) in k-mers/s — near 1.0 the streams ran one after the other (e.g. shared hardware queues);
     #   (e) (1) again with HIP events around every launch: the per-launch kernel time of the roofline (the events
     #       cost 6-10 µs per step, scripts/step_overhead.py, so (p) and (1) run without them).
-    n_reg = max(1, int(getattr(a, "regions", 5)))
+    # Without --full: (p) alone, in one region of exactly K timed steps, and of the checks below only `counts`.
+    full = bool(getattr(a, "full", False))
+    with_lf, with_pcie, with_cpu = with_lf and full, with_pcie and full, with_cpu and full
+    n_reg = max(1, int(getattr(a, "regions", 0)) or (5 if full else 1))
     el_p, el_1, el_e, kms, enq = [], [], [], [], []
     snap_p = snap_job = None
     ran_p = [0] * len(bufs)
@@ -534,9 +594,12 @@ def run_workload(ctx: Ctx, cfg_no: int, k: int, n_reads: int, mode: str, steps: 
         enq.append(rot["enqueue_s"])
         timed_kmers = rot["kmers"]
         ran_p = list(rot["ran"])
-        if r_i == n_reg - 1:  # every stream's counters of the last pipelined job (checked below)
+        if r_i == n_reg - 1:  # every stream's counters of the last pipelined job (checked below; --dump-outputs)
             snap_p = [counters(b["cnt"], b["w"]) for b in bufs]
             snap_job = counters(job_cnt, job_w) if (ctx.comm is not None and not per_step) else None
+            last_stream = (rot["i"] - 1) % rot["n"]  # the stream of the last timed step
+        if not full:
+            continue
         if n_str > 1:
             el_1.append(timed_run(steps, 0, events=False)[0])
             kmers_1 = rot["kmers"]
@@ -544,22 +607,23 @@ def run_workload(ctx: Ctx, cfg_no: int, k: int, n_reads: int, mode: str, steps: 
         el_e.append(e)
         kms.append(kmsum / max(1, launches))
     elapsed = float(np.median(el_p))
-    elapsed_ev = float(np.median(el_e))
-    kernel_med = float(np.median(kms))
+    elapsed_ev = float(np.median(el_e)) if el_e else None
+    kernel_med = float(np.median(kms)) if kms else None
+    prepared["last_outputs"] = timed_outputs(snap_p, snap_job, ran_p, last_stream)
     # Checks of the last pipelined job: every stream's counters equal (scans of that stream) x its batch scanned
     # alone on one stream (per step mode: one scan, all-reduced); the job's all-reduced total equals the sum over
     # the streams of the same, all-reduced. `counts`: batch 0 scanned alone and all-reduced (the line's check, and
     # what the CPU baseline is compared with).
-    alone_local = [scan_once(b, reduce=False) if ran_p[i] else None for i, b in enumerate(bufs)]
+    alone_local = [scan_once(b, reduce=False) if (full and ran_p[i]) else None for i, b in enumerate(bufs)]
     counts_t = scan_once(bufs[0], reduce=True)
     for i, b in enumerate(bufs):
-        if not ran_p[i]:
+        if not ran_p[i] or not full:
             continue  # (fewer timed steps than streams: this stream's batch never ran)
         want = (scan_once(b, reduce=True) if ctx.comm is not None else alone_local[i]) if per_step else \
             times(alone_local[i], ran_p[i])
         if not same(snap_p[i], want, rtol=1e-11):
             raise RuntimeError(f"the pipelined scans of stream {i} disagree with its batch scanned alone")
-    if snap_job is not None:
+    if snap_job is not None and full:
         tot = None
         for i, b in enumerate(bufs):
             if ran_p[i]:
@@ -568,7 +632,8 @@ def run_workload(ctx: Ctx, cfg_no: int, k: int, n_reads: int, mode: str, steps: 
         if not same(snap_job, tot, rtol=1e-11):
             raise RuntimeError("the job's all-reduced counters disagree with its batches scanned alone")
     # batch 0's counters after a one-stream timed run: `steps` scans summed (job), or one scan (+ all-reduced) per step
-    job1 = ((counts_t[0] if ctx.comm is not None else alone_local[0][0]) if per_step else alone_local[0][0] * steps)
+    job1 = ((counts_t[0] if ctx.comm is not None else alone_local[0][0]) if per_step else
+            alone_local[0][0] * steps) if full else None
     d_counts.copy_(torch.from_numpy(counts_t[0]).to(ctx.dev_t))
     if local:
         d_w.copy_(torch.from_numpy(counts_t[1]).to(ctx.dev_t))
@@ -578,17 +643,17 @@ def run_workload(ctx: Ctx, cfg_no: int, k: int, n_reads: int, mode: str, steps: 
         "value_min": timed_kmers * ctx.world / max(el_p), "value_max": timed_kmers * ctx.world / min(el_p),
         "ms_per_step": [round(x / steps * 1e3, 5) for x in el_p],
         "host_enqueue_ms_per_step": [round(x / steps * 1e3, 5) for x in enq],
-        "avg_kernel_ms": [round(x, 5) for x in kms],
-        "avg_kernel_ms_median": kernel_med, "avg_kernel_ms_min": min(kms), "avg_kernel_ms_max": max(kms),
     }
+    if kms:
+        timing.update({
+            "avg_kernel_ms": [round(x, 5) for x in kms],
+            "avg_kernel_ms_median": kernel_med, "avg_kernel_ms_min": min(kms), "avg_kernel_ms_max": max(kms)})
     if el_1:
         e1 = float(np.median(el_1))
         timing["one_stream"] = {"value": kmers_1 * ctx.world / e1, "ms_per_step": e1 / steps * 1e3,
                                 "ms_per_step_all": [round(x / steps * 1e3, 5) for x in el_1]}
         # k-mers/s pipelined over k-mers/s on one stream (equal-length reads: one-stream ms per step / pipelined)
         timing["overlap"] = (timed_kmers / elapsed) / (kmers_1 / e1)
-    launches = steps
-    kernel_ms = kernel_med * launches
     counts = d_counts.cpu().numpy()
     weights = d_w.cpu().numpy() if local else None
     table_on = bool(ktab["table_bytes"])
@@ -619,9 +684,8 @@ def run_workload(ctx: Ctx, cfg_no: int, k: int, n_reads: int, mode: str, steps: 
 
     total_kmers = timed_kmers * ctx.world
     value = total_kmers / elapsed
-    avg_kernel_s = (kernel_ms / 1e3) / max(1, launches)
     ax_stats = req = None
-    if hot_kernel == 3 and not os.environ.get("SPEQ_BENCH_NO_STATS"):
+    if full and hot_kernel == 3 and not os.environ.get("SPEQ_BENCH_NO_STATS"):
         # one untimed launch of the instrumented twin: the same scan (checked equal), plus its work counters
         d_counts.zero_()
         if local:
@@ -633,9 +697,11 @@ def run_workload(ctx: Ctx, cfg_no: int, k: int, n_reads: int, mode: str, steps: 
         req = ax_request_bytes(ax_stats, k, reads.n, local)
     compulsory = 2.0 * read_bytes + 8.0 * (reads.n + 1)  # bases + qualities + read offsets
     key = workload_key(cfg_no, k, mode, n_reads, KERNEL_TAG.get(hot_kernel, "lf"), qual_profile, err)
-    roofline = roofline_of(key, avg_kernel_s, req["total"] if req else None, compulsory, k, kmers_per_step)
-    roofline["kernel"] = KERNEL_NAME.get(hot_kernel, str(hot_kernel))
-    roofline["launches_timed"] = launches
+    roofline = None  # (needs the per-launch kernel time of the runs with events: --full)
+    if kernel_med is not None:
+        roofline = roofline_of(key, kernel_med / 1e3, req["total"] if req else None, compulsory, k, kmers_per_step)
+        roofline["kernel"] = KERNEL_NAME.get(hot_kernel, str(hot_kernel))
+        roofline["launches_timed"] = steps
 
     pcie = None
     if with_pcie:
@@ -669,8 +735,9 @@ def run_workload(ctx: Ctx, cfg_no: int, k: int, n_reads: int, mode: str, steps: 
     check = {"T": int(counts[0]), "ambiguous": int(counts[1]), "U_sha1": u_sha1(counts[2:]),
              **({"W_sum": float(weights.sum())} if weights is not None else {})}
     out = {
-        "value": value, "ms_per_step": elapsed / steps * 1e3, "avg_kernel_ms": avg_kernel_s * 1e3,
-        "ms_per_step_with_events": elapsed_ev / steps * 1e3, "k": k, "streams": n_str,
+        "value": value, "ms_per_step": elapsed / steps * 1e3, "avg_kernel_ms": kernel_med,
+        "ms_per_step_with_events": elapsed_ev / steps * 1e3 if elapsed_ev is not None else None, "k": k,
+        "streams": n_str,
         "mode": mode,
         "workload": f"BASELINE config {cfg_no}: {c['n_variants']} variants x {c['n_isolates']} isolates x "
                     f"{c['length']} bp, {n_reads} x 150 bp {'pairs' if paired else 'reads'} per GPU, k={k}, {mode}"
@@ -721,7 +788,7 @@ def compact_line(r: dict) -> dict:
 def compact_result(head: dict, lines: dict, meta: dict) -> dict:
     """The ONE stdout JSON line (BASELINE keys + roofline + cpu_baseline + compact secondary lines), < LINE_LIMIT
     bytes; everything else goes to the detail file."""
-    rf = dict(head["roofline"])
+    rf = dict(head["roofline"] or {})  # (None without --full, like one_stream, overlap and the kernel times)
     tm = head["timing"]
     roof = {k: rf.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_frac",
                                    "frac_basis", "avg_kernel_ms", "traffic_source", "traffic_rocprof_kernel_ms",
@@ -732,24 +799,29 @@ def compact_result(head: dict, lines: dict, meta: dict) -> dict:
         "steps": meta["steps"], "warmup": meta["warmup"], "ms_per_step": head["ms_per_step"],
         "ms_per_step_with_events": head.get("ms_per_step_with_events"),
         "streams": head.get("streams", 1),
+        "full": bool(meta.get("full", True)),
         "timing": f"value: the median of {tm['regions']} timed regions of K steps without per-launch events" + (
-            f", step i on HIP stream i % {head.get('streams')} (consecutive batches overlap); one_stream: the same "
-            "steps on one stream in each region (overlap = value / one_stream.value)"
-            if head.get("streams", 1) > 1 else "") + "; roofline.avg_kernel_ms: the median over the regions of "
-                  "the same K steps on one stream with HIP events around every launch",
+            f", step i on HIP stream i % {head.get('streams')} (consecutive batches overlap)"
+            if head.get("streams", 1) > 1 else "") + (
+            "; one_stream: the same steps on one stream in each region (overlap = value / one_stream.value)"
+            if "one_stream" in tm else "") + (
+            "; roofline.avg_kernel_ms: the median over the regions of the same K steps on one stream with HIP events "
+            "around every launch" if rf else ""),
         "value_min": tm["value_min"], "value_max": tm["value_max"],
         "one_stream": {k2: tm["one_stream"][k2] for k2 in ("value", "ms_per_step")} if "one_stream" in tm else None,
         "overlap": tm.get("overlap"),
-        "avg_kernel_ms_min_max": [tm["avg_kernel_ms_min"], tm["avg_kernel_ms_max"]],
+        "avg_kernel_ms_min_max": [tm.get("avg_kernel_ms_min"), tm.get("avg_kernel_ms_max")],
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
         "data": "synthetic (splitmix64 references/reads, SURVEY.md §8(d))",
         "config": meta["config"],
-        "roofline": roof,
+        "roofline": roof if rf else None,
         "cpu_baseline": compact_cpu(head.get("cpu_baseline")),
         "check": head["check"],
         "lines": {name: compact_line(r) for name, r in lines.items() if r},
         "detail_file": meta.get("detail_file"),
     }
+    if meta.get("dumped") is not None:
+        out["dumped"] = meta["dumped"]
     s = json.dumps(out)
     if len(s) > LINE_LIMIT:  # never let the line outgrow what the driver parses: drop the optional fields first
         for r in out["lines"].values():
@@ -780,12 +852,15 @@ def main(argv=None):
                               with_pcie=not a.no_pcie, with_cpu=not a.no_cpu_baseline, cpu_seconds=a.cpu_seconds,
                               qual_profile=a.qual, err=a.err, cpu_extra_ports=True)
     dev = prep["dev"]
+    # every rank writes what its own last timed step computed (rank r > 0 into DIR/rank<r>)
+    dumped = dump_outputs(a.dump_outputs if ctx.rank == 0 else os.path.join(a.dump_outputs, f"rank{ctx.rank}"),
+                          prep["last_outputs"]) if a.dump_outputs else None
     lines = {}
     only = set(x for x in a.only.split(",") if x)
     want = lambda name: not only or name in only  # noqa: E731
     cpu_on = not a.no_cpu_baseline
     short_cpu = max(4.0, a.cpu_seconds / 2)
-    if not a.no_extra and a.config == 2 and not a.k and not a.reads and a.qual == "q40" and a.err == 0.001:
+    if a.full and not a.no_extra and a.config == 2 and not a.k and not a.reads and a.qual == "q40" and a.err == 0.001:
         other = "local" if a.mode == "global" else "global"
         if want(f"{other}_mode"):
             lines[f"{other}_mode"], _ = run_workload(ctx, 2, k, n_reads, other, a.steps, a.warmup, with_lf=False,
@@ -831,7 +906,9 @@ def main(argv=None):
             p5["dev"].close()
 
     if ctx.rank == 0:
-        detail_path = a.detail or os.path.join(ROOT, "profiles", "r06", f"bench_detail_n{ctx.world}.json")
+        # the detail file: where --detail says; with --full by default profiles/r06/bench_detail_n<N>.json
+        detail_path = a.detail or (os.path.join(ROOT, "profiles", "r06", f"bench_detail_n{ctx.world}.json")
+                                   if a.full else "")
         config = {
             "workload": head["workload"],
             "k": k, "reads_per_gpu": n_reads, "paired": head["paired"], "mode": a.mode,
@@ -845,18 +922,19 @@ def main(argv=None):
             "kmer_table": {"bytes": head["kmer_table"]["bytes"], "build_s": head["kmer_table"]["build_s"]},
         }
         meta = {"metric": "k-mers scanned/sec (whole node) at k=%d, 150 bp reads" % k, "n_gpus": ctx.world,
-                "steps": a.steps, "warmup": a.warmup, "config": config,
-                "detail_file": os.path.relpath(detail_path, ROOT) if detail_path.startswith(ROOT) else detail_path}
+                "steps": a.steps, "warmup": a.warmup, "config": config, "full": a.full, "dumped": dumped,
+                "detail_file": (os.path.relpath(detail_path, ROOT) if detail_path.startswith(ROOT) else detail_path)
+                or None}
         out = compact_result(head, lines, meta)
         try:
-            os.makedirs(os.path.dirname(detail_path), exist_ok=True)
-            with open(detail_path, "w") as f:
-                json.dump({"compact": out, "head": head, "lines": lines,
-                           "tuning": {"blocks_per_cu": dev.tuning("blocks_per_cu"),
-                                      "grid_blocks": dev.tuning("grid_blocks"), "prefix_q": a.prefix_q,
-                                      "pair_steps": a.pair_steps, "triple_steps": a.triple_steps,
-                                      "label_table": int(prep["idx"].info().label_table)},
-                           "host": host_cpu_info()}, f, indent=1, default=str)
+            if detail_path:
+                write_detail(detail_path, {
+                    "compact": out, "head": head, "lines": lines,
+                    "tuning": {"blocks_per_cu": dev.tuning("blocks_per_cu"),
+                               "grid_blocks": dev.tuning("grid_blocks"), "prefix_q": a.prefix_q,
+                               "pair_steps": a.pair_steps, "triple_steps": a.triple_steps,
+                               "label_table": int(prep["idx"].info().label_table)},
+                    "host": host_cpu_info()})
         except OSError as e:
             out["detail_file"] = f"not written: {e}"
         print(json.dumps(out), flush=True)
@@ -864,6 +942,12 @@ def main(argv=None):
         ctx.comm.close()
     if ctx.world > 1:
         ctx.dist.destroy_process_group()
+
+
+def write_detail(path: str, detail: dict) -> None:
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(detail, f, indent=1, default=str)
 
 
 def write_fastq(path: str, reads, chunk: int = 1_000_000) -> int:

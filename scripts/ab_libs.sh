@@ -9,7 +9,7 @@ out=gpurun_out/ab_libs.jsonl
 for rep in $(seq 1 ${AB_REPEAT:-2}); do
   for v in $VARS; do
     if [ "$v" = default ]; then lib=""; else lib="build/variants/$v/libspeq_scan.so"; fi
-    SPEQ_LIB_PATH=$lib timeout -k 10 200 python bench.py --no-extra --no-cpu-baseline --no-pcie --no-lf-compare \
+    SPEQ_LIB_PATH=$lib timeout -k 10 200 python bench.py --full --no-extra --no-cpu-baseline --no-pcie --no-lf-compare \
         --detail gpurun_out/ab_detail_$v.json "$@" > gpurun_out/ab_one.json 2> gpurun_out/ab_libs.err || { echo "variant $v failed"; tail -5 gpurun_out/ab_libs.err; exit 1; }
     python - "$v" "$rep" "$*" >> $out <<'PY'
 import json, sys

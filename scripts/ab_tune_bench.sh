@@ -7,7 +7,7 @@ VARS=$1; shift
 out=gpurun_out/ab_tune_bench.jsonl
 for rep in $(seq 1 ${AB_REPEAT:-2}); do
   for v in $VARS; do
-    timeout -k 10 240 python bench.py --no-extra --no-cpu-baseline --no-pcie --no-lf-compare --tune $v \
+    timeout -k 10 240 python bench.py --full --no-extra --no-cpu-baseline --no-pcie --no-lf-compare --tune $v \
         --detail gpurun_out/ab_tune_detail.json "$@" > gpurun_out/ab_tune_one.json 2> gpurun_out/ab_tune.err || { echo "tune $v failed"; tail -5 gpurun_out/ab_tune.err; exit 1; }
     python - "$v" "$rep" "$*" >> $out <<'PY'
 import json, sys

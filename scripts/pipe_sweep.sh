@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 GRIDS=${1:-"1280 1024 768 640"}; STREAMS=${2:-"2"}; shift 2
 out=gpurun_out/pipe_sweep.jsonl
 for s in $STREAMS; do for g in $GRIDS; do
-  timeout -k 10 200 python bench.py --no-extra --no-cpu-baseline --no-pcie --no-lf-compare --streams $s \
+  timeout -k 10 200 python bench.py --full --no-extra --no-cpu-baseline --no-pcie --no-lf-compare --streams $s \
       --tune grid_blocks_ax=$g --detail gpurun_out/pipe_sweep_detail.json "$@" > gpurun_out/pipe_sweep_one.json 2> gpurun_out/pipe_sweep.err || exit 1
   python - "$g" "$s" >> $out <<'PY'
 import json, sys

@@ -64,6 +64,50 @@ def test_compact_line_is_small_and_complete():
         assert "U" not in r["check"]
 
 
+def test_plain_line_keeps_the_headline_keys():
+    """Without --full the head has no roofline, one-stream or kernel times: the line still carries the headline."""
+    head = _line()
+    head.update(roofline=None, cpu_baseline=None, avg_kernel_ms=None)
+    head["timing"] = {"regions": 1, "steps_per_region": 20, "value_median": 5.1e11, "value_min": 5.1e11,
+                      "value_max": 5.1e11, "ms_per_step": [0.2561234]}
+    meta = {"metric": "k-mers scanned/sec (whole node) at k=21, 150 bp reads", "n_gpus": 1, "steps": 20, "warmup": 2,
+            "detail_file": None, "full": False, "dumped": ["counts", "counts_stream0"], "config": {"k": 21}}
+    out = bench.compact_result(head, {}, meta)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+        assert out[key] is not None, key
+    assert out["full"] is False and out["ms_per_step"] == pytest.approx(0.2561234)
+    assert out["roofline"] is None and out["one_stream"] is None and out["overlap"] is None and out["lines"] == {}
+    assert out["timing"] == "value: the median of 1 timed regions of K steps without per-launch events"
+    assert out["dumped"] == ["counts", "counts_stream0"] and out["check"] == head["check"]
+
+
+def test_parse_args_full_and_dump_outputs():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "1"])
+    assert (a.full, a.dump_outputs, a.steps, a.regions) == (False, "", 7, 0)
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_timed_outputs_and_dump(tmp_path):
+    import numpy as np
+    cnt = [np.arange(5, dtype=np.int64) * 3, np.arange(5, dtype=np.int64) * 2, np.zeros(5, dtype=np.int64)]
+    w = [np.full(3, 0.5), np.full(3, 0.25), np.zeros(3)]
+    arrays = bench.timed_outputs([(c, x) for c, x in zip(cnt, w)], None, [3, 2, 0], 1)
+    assert sorted(arrays) == ["counts", "counts_stream0", "counts_stream1", "weights", "weights_stream0",
+                              "weights_stream1"]  # (stream 2 ran no step)
+    assert np.array_equal(arrays["counts"], cnt[1]) and np.array_equal(arrays["weights"], w[1])
+    arrays = bench.timed_outputs([(c, None) for c in cnt], (cnt[0] + cnt[1], None), [3, 2, 0], 0)
+    assert sorted(arrays) == ["counts", "counts_stream0", "counts_stream1", "job_counts"]
+    names = bench.dump_outputs(str(tmp_path / "d" / "e"), arrays)
+    assert names == sorted(arrays)
+    for name in names:
+        v = np.load(tmp_path / "d" / "e" / (name + ".npy"))
+        assert v.dtype == np.float64 and np.array_equal(v, arrays[name])
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros((bench.DUMP_LIMIT >> 3) + 1)})
+    assert not (tmp_path / "big").exists()
+
+
 def test_roofline_uses_calibrated_fabric_bytes(tmp_path, monkeypatch):
     prof = tmp_path / "profiles"
     prof.mkdir()

@@ -32,7 +32,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path, streams):
     bench itself against its batch scanned again on one stream."""
     detail = tmp_path / "detail.json"
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--streams", str(streams),
+           "--full", "--streams", str(streams),
            "--reads", str(READS), "--no-extra", "--no-cpu-baseline", "--no-pcie", "--no-lf-compare",
            "--detail", str(detail)]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
@@ -67,6 +67,53 @@ def test_bench_two_ranks_on_one_gpu(tmp_path, streams):
     assert out["value_min"] <= out["value"] <= out["value_max"]
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full): one timed region of exactly --steps steps, no secondary measurement, and
+    --dump-outputs writes what the timed scans left in their callers' counters. Steps 5 after 2 warm-up steps on two
+    streams: timed step j runs on stream (2 + j) % 2, so stream 0's counters hold 3 scans of batch 0 (reads 0 .. n-1),
+    stream 1's hold 2 scans of batch 1 (reads n .. 2n-1), and the last step ran on stream 0."""
+    dump = tmp_path / "out"
+    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+           "--reads", str(READS), "--dump-outputs", str(dump)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["full"] is False and out["steps"] == 5 and out["n_gpus"] == 1
+    assert out["unit"] == "k-mers/s" and out["higher_is_better"] is True and out["dtype"] == "u32"
+    assert out["lines"] == {} and out["cpu_baseline"] is None and out["roofline"] is None and out["one_stream"] is None
+    assert out["detail_file"] is None and os.listdir(tmp_path) == ["out"]
+    assert "median of 1 timed regions" in out["timing"]
+    assert sorted(os.listdir(dump)) == ["counts.npy", "counts_stream0.npy", "counts_stream1.npy"]
+    assert out["dumped"] == ["counts", "counts_stream0", "counts_stream1"]
+
+    c = synth.CONFIGS[2]
+    ref = synth.make_reference(c["n_variants"], c["n_isolates"], c["length"])
+    idx = FmIndex.build(ref.records, ref.groups, c["n_variants"], prefix_q=12, pair_steps=True, label_table="auto",
+                        threads=16, gpu_device=0, triple_steps=True)
+    dev = DeviceIndex(idx, 0)
+    try:
+        reads = synth.make_reads(ref, 2 * READS, err_rate=0.001)
+        h = int(reads.offsets[READS])
+        r0 = dev.scan(reads.seq[:h].tobytes(), reads.qual[:h].tobytes(), reads.offsets[:READS + 1], k=21)
+        r1 = dev.scan(reads.seq[h:].tobytes(), reads.qual[h:].tobytes(), reads.offsets[READS:] - h, k=21)
+    finally:
+        dev.close()
+    want = lambda r, n: n * np.array([r.total, r.ambiguous] + r.unique.tolist(), dtype=np.float64)  # noqa: E731
+    got = {name: np.load(dump / (name + ".npy")) for name in out["dumped"]}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["counts_stream0"], want(r0, 3))
+    assert np.array_equal(got["counts_stream1"], want(r1, 2))
+    assert np.array_equal(got["counts"], got["counts_stream0"])
+    assert (out["check"]["T"], out["check"]["ambiguous"], out["check"]["U_sha1"]) == (
+        r0.total, r0.ambiguous, bench.u_sha1(r0.unique))
+    # value = the timed steps' k-mers / their time: 3 x batch 0 + 2 x batch 1 in 5 x ms_per_step
+    kmers = 5 * READS * (150 - 21 + 1)
+    assert out["value"] == pytest.approx(kmers / (out["ms_per_step"] * 5 / 1e3), rel=1e-6)
+
+
 @pytest.mark.parametrize("allreduce", ["job", "step"])
 def test_bench_rccl_one_rank_keeps_batches_in_flight(tmp_path, allreduce):
     """the 8-GPU line's code path on one GPU — torch's NCCL process group and the product's RCCL
@@ -78,7 +125,8 @@ def test_bench_rccl_one_rank_keeps_batches_in_flight(tmp_path, allreduce):
     n = 1_000_000
     detail = tmp_path / "detail.json"
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--transport", "rccl", "--steps", "20",
-           "--warmup", "3", "--streams", "2", "--allreduce", allreduce, "--no-extra", "--no-cpu-baseline", "--no-pcie", "--no-lf-compare",
+           "--warmup", "3", "--full", "--streams", "2", "--allreduce", allreduce, "--no-extra", "--no-cpu-baseline",
+           "--no-pcie", "--no-lf-compare",
            "--detail", str(detail)]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["SPEQ_BENCH_NO_STATS"] = "1"
