@@ -77,12 +77,14 @@ axvariant: $(filter-out $(OBJDIR)/ax_scan.o,$(LIB_OBJS))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/variants/$(NAME)/libspeq_scan.so \
 	    build/variants/$(NAME)/ax_scan.o $^ -L/opt/rocm/lib -lamdhip64 -lz -lpthread -ldl -Wl,-rpath,/opt/rocm/lib
 
-# Every compile-time knob of k_scan_ax forced off its default, three builds (tests/test_gpu_ax_knobs.py runs the
-# parity suite tests/ax_knob_suite.py against each): make axknobs -> build/axknobs/<name>/libspeq_scan.so
+# Every compile-time knob of k_scan_ax forced off its default, four builds (tests/test_gpu_ax_knobs.py, and
+# tests/test_gpu_sproof_knob.py for kv4, run the parity suite tests/ax_knob_suite.py against each):
+# make axknobs -> build/axknobs/<name>/libspeq_scan.so
 AXKNOB_kv1 := -DSPEQ_AX_SU=1 -DSPEQ_AX_SU_LOCAL=2 -DSPEQ_AX_REFILL=8 -DSPEQ_AX_BLOCKED=32 -DSPEQ_AX_P2_MARGIN=64 -DSPEQ_AX_PRIO_MIN=0 -DSPEQ_AX_WL=64 -DSPEQ_AX_MTILES=0
 AXKNOB_kv2 := -DSPEQ_AX_WPB=2 -DSPEQ_AX_MIN_WAVES=4 -DSPEQ_AX_MIN_WAVES_LOCAL=3 -DSPEQ_AX_DEF_GLOBAL=192 -DSPEQ_AX_DEF_LOCAL=128
 AXKNOB_kv3 := -DSPEQ_AX_SPEC_HW=1 -DSPEQ_AX_PRIO=0 -DSPEQ_AX_MPROOF=0
-AXKNOBS    := kv1 kv2 kv3
+AXKNOB_kv4 := -DSPEQ_AX_SPROOF=0
+AXKNOBS    := kv1 kv2 kv3 kv4
 AXKNOB_OTHER := $(filter-out $(OBJDIR)/ax_scan.o,$(LIB_OBJS))
 
 axknobs: $(foreach v,$(AXKNOBS),build/axknobs/$(v)/libspeq_scan.so)

@@ -158,8 +158,11 @@ int speq_scan_reads_device(speq_device_index* d, const uint8_t* d_seq, const uin
  * [25] deferred-window passes (per wave), [26] cycles of the Bloom-filter part of phase 2, [27] phase-2 probe rounds
  * of the filter's survivors (per wave), [28] / [29] cycles of refills before their staging loads / in their staging
  * batches, [30] the longest wave's loop cycles (a maximum), [31] waves, [32..36] loop cycles summed over the waves of
- * blocks 0-255, 256-511, 512-767, 768-1023 and 1024 on. Fails with SPEQ_E_ARG when the scan does not use that kernel. */
-#define SPEQ_AX_STATS_N 37
+ * blocks 0-255, 256-511, 512-767, 768-1023 and 1024 on, [37] probes of the substitution bitmap (tuning "ax_sproof"),
+ * [38] windows over a mismatch dropped on its proof (not looked up, not deferred), [39] proofs whose continued run met
+ * a second mismatch within k - 1 bases (the windows over both deferred). Fails with SPEQ_E_ARG when the scan does not
+ * use that kernel. */
+#define SPEQ_AX_STATS_N 40
 int speq_scan_reads_device_stats(speq_device_index* d, const uint8_t* d_seq, const uint8_t* d_qual,
                                  const uint64_t* d_offsets, uint64_t n_reads, const speq_scan_params* params,
                                  uint64_t* d_counts, double* d_weights, uint64_t* stats);
@@ -370,7 +373,10 @@ void speq_groupings_free(speq_groupings* g);
  *                  per CU (0: as registers/LDS allow), "ax_generations" grid = 1..16 times the resident blocks
  *                  (default 1: one persistent generation), "ax_mproof" m-mer absence proofs of the windows around a
  *                  mismatch (1 default: known and unknown mismatches, 2: known ones only, 0: off; results are the
- *                  same); "last_kernel" (read only) the kernel of the last scan. */
+ *                  same), "ax_sproof" substitution-bitmap proofs of the windows over a known mismatch (1: on, 0: off,
+ *                  2 default: on for the k whose structures have no m-mer filter; the bitmap of a k is built by
+ *                  speq_device_prepare or the first scan that uses it; results are the same);
+ *                  "last_kernel" (read only) the kernel of the last scan. */
 int speq_device_set_tuning(speq_device_index* d, const char* key, int64_t value);
 int speq_device_get_tuning(const speq_device_index* d, const char* key, int64_t* value);
 
@@ -384,6 +390,12 @@ int speq_device_get_tuning(const speq_device_index* d, const char* key, int64_t*
  * searches each window from scratch (fm_scanner.cpp:208). */
 int speq_device_prepare(speq_device_index* d, uint32_t k, uint64_t* distinct_kmers, uint64_t* table_bytes,
                         double* build_ms);
+
+/* Test accessor: copies the substitution bitmap of k (bit x of word x / 64: no single-base substitution at text
+ * position x in any of the k windows over x gives a k-mer of the texts) to `words` (host,
+ * u64[n_words], n_words >= ceil(n / 64)); builds the structures of k and the bitmap when they are missing. Fails with
+ * SPEQ_E_ARG when the anchor-and-extend scan does not take k. Blocking. */
+int speq_device_sproof_bitmap(speq_device_index* d, uint32_t k, uint64_t* words, uint64_t n_words);
 
 /* ---- kernel timing (HIP events on the launch stream; bench/roofline support) ----
  * Returns the summed elapsed milliseconds of the scan kernels launched by speq_scan_reads_device on

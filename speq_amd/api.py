@@ -194,7 +194,8 @@ class DeviceIndex:
                      "run_tallied", "run_granules", "refills", "busy_1_4", "busy_5_16", "busy_17_32", "busy_33_64",
                      "cyc_refill", "cyc_lookup", "cyc_run", "cyc_phase2", "cyc_total", "p2_passes",
                      "cyc_p2_filter", "p2_rounds", "cyc_ref_pre", "cyc_ref_stage", "cyc_wave_max", "waves",
-                     "cyc_gen0", "cyc_gen1", "cyc_gen2", "cyc_gen3", "cyc_gen4")
+                     "cyc_gen0", "cyc_gen1", "cyc_gen2", "cyc_gen3", "cyc_gen4",
+                     "sproof_probes", "sproof_windows", "sproof_partial")
 
     def scan_device_stats(self, d_seq: int, d_qual: int, d_offsets: int, n_reads: int, k: int, d_counts: int,
                           d_weights: int = 0, phred_cutoff: int = 30, paired: bool = False,
@@ -272,6 +273,14 @@ class DeviceIndex:
         n, b, ms = C.c_uint64(), C.c_uint64(), C.c_double()
         check(lib().speq_device_prepare(self._h, k, C.byref(n), C.byref(b), C.byref(ms)))
         return {"distinct_kmers": n.value, "table_bytes": b.value, "build_ms": ms.value}
+
+    def sproof_bitmap(self, k: int) -> np.ndarray:
+        """Test accessor (speq_device_sproof_bitmap): the substitution bitmap S of the prepared k, one bool per text
+        position (S[x]: no single-base substitution at x in any of the k windows over x gives an indexed k-mer)."""
+        n = int(self.index.info().n)
+        words = np.zeros((n + 63) // 64, dtype=np.uint64)
+        check(lib().speq_device_sproof_bitmap(self._h, k, _u64p(words), len(words)))
+        return np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
 
     def timing(self, on: bool) -> None:
         check(lib().speq_timing_enable(self._h, int(on)))

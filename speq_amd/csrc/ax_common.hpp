@@ -26,6 +26,8 @@ struct AxView {
                                // covers both, so a lookup iteration loads buckets and m-mer filter words alike)
     uint32_t m;                // m of the m-mer filter (0: off)
     uint32_t mtiles;           // 1: also probe windows whose mismatch is unknown (lane state 6)
+    uint32_t s_off;            // byte offset of the substitution bitmap S from atab (under the same descriptor)
+    uint32_t s_bytes;          // its bytes incl. the 16-B load slack (0: no substitution proofs, lane state 7 unused)
     uint32_t G;
 };
 }  // namespace speq_dev
@@ -35,9 +37,10 @@ namespace {
 using namespace speq_dev;
 
 // Compile-time knobs (A/B only; every one is run through the parity tests forced to a non-default value by
-// tests/test_gpu_ax_knobs.py over `make axknobs` builds), sixteen: SPEQ_AX_DEF_LOCAL, SPEQ_AX_DEF_GLOBAL, SPEQ_AX_WL,
+// tests/test_gpu_ax_knobs.py and tests/test_gpu_sproof_knob.py over `make axknobs` builds), seventeen: SPEQ_AX_DEF_LOCAL, SPEQ_AX_DEF_GLOBAL, SPEQ_AX_WL,
 // SPEQ_AX_WPB, SPEQ_AX_SU, SPEQ_AX_SU_LOCAL, SPEQ_AX_MIN_WAVES, SPEQ_AX_MIN_WAVES_LOCAL, SPEQ_AX_REFILL, SPEQ_AX_BLOCKED,
-// SPEQ_AX_SPEC_HW, SPEQ_AX_PRIO, SPEQ_AX_PRIO_MIN, SPEQ_AX_P2_MARGIN, SPEQ_AX_MPROOF, SPEQ_AX_MTILES. Measured losers
+// SPEQ_AX_SPEC_HW, SPEQ_AX_PRIO, SPEQ_AX_PRIO_MIN, SPEQ_AX_P2_MARGIN, SPEQ_AX_MPROOF, SPEQ_AX_MTILES, SPEQ_AX_SPROOF.
+// Measured losers
 // of rounds 3-5 (a cuckoo anchor table, lowest / first-claimant representatives, a dynamic tail, generation-weighted
 // pools, offset prefetch, speculative runs in global mode, a minimizer-keyed filter, workgroup-shared pools) were
 // removed; DESIGN.md §4f-§4g keep their numbers.
@@ -121,6 +124,9 @@ enum : uint32_t {
     AXS_CYC_GEN2,
     AXS_CYC_GEN3,
     AXS_CYC_GEN4,
+    AXS_SPROOF_PROBES,   // probes of the substitution bitmap (lanes in state 7)
+    AXS_SPROOF_WINDOWS,  // valid windows over a mismatch dropped on its proof (neither looked up nor deferred)
+    AXS_SPROOF_PARTIAL,  // proofs whose continued run met a second mismatch within k - 1 bases
     AXS_N
 };
 static_assert(AXS_N == SPEQ_AX_STATS_N, "speq_scan.h SPEQ_AX_STATS_N");
@@ -318,6 +324,13 @@ constexpr uint32_t AX_WPB = SPEQ_AX_WPB, AX_THREADS = 64 * SPEQ_AX_WPB;
 #endif                    // tuning ax_mproof)
 #ifndef SPEQ_AX_MTILES  // 1: ... and for an absent window whose mismatch is unknown (lane state 6; A/B knob)
 #define SPEQ_AX_MTILES 1
+#endif
+// SPEQ_AX_SPROOF 1: the windows over a known mismatch at a text position whose bit is set in the substitution bitmap are
+// absent without a lookup or a deferral (lane state 7; A/B knob; runtime: tuning ax_sproof). Forced to 0
+// by the `kv4` build of `make axknobs`, which tests/test_gpu_sproof_knob.py runs through the knob suite (the sixteen
+// knobs of tests/test_gpu_ax_knobs.py's list are the `#ifndef` ones above and below)
+#if !defined(SPEQ_AX_SPROOF)
+#define SPEQ_AX_SPROOF 1
 #endif
 #ifndef SPEQ_AX_P2_MARGIN  // the deferred-window pass also runs when fewer than this many list entries are free
 #define SPEQ_AX_P2_MARGIN 256u  // (A/B knob; a deferral that finds the list full waits for the pass: lane state 3)

@@ -271,6 +271,72 @@ __global__ void k_ax_mfilter(const uint64_t* __restrict__ t2, const uint64_t* __
     }
 }
 
+// Pass E (on demand: ensure_ax_sproof): the substitution bitmap S, one bit per text position x. S[x] = 1 iff every one of
+// the k windows that contain x lies inside x's text and holds no N, and for each of them and each of the three other
+// bases at x the substituted k-mer occurs nowhere in the texts: its bits are missing from the Bloom filter, or its chain
+// in the anchor table ends at an empty slot without a slot whose text equals it (what phase 2 of the scan does). A read
+// window that equals such a text window except at x is then absent, whatever the read's base at x (k_scan_ax, lane
+// state 7). Anything else is 0, which only keeps the scan on its lookup-and-defer path. One thread per
+// position; a wave writes the 64 bits of its 64 positions.
+__global__ void k_ax_sbitmap(const uint64_t* __restrict__ t2, const uint64_t* __restrict__ tbad, uint64_t n, uint32_t k,
+                             const unsigned long long* __restrict__ atab, uint64_t nb,
+                             const unsigned long long* __restrict__ filt, uint64_t nf,
+                             unsigned long long* __restrict__ S, uint64_t s_words) {
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < s_words * 64u;
+         base += (uint64_t)gridDim.x * blockDim.x) {  // (block-uniform trip count: the ballot below sees whole waves)
+        const uint64_t x = base + threadIdx.x;
+        bool ok = x + 1u >= k && x + k <= n;
+        if (ok)  // no non-ACGT symbol (N, separator, terminator) in [x - k + 1, x + k)
+            for (uint64_t b = x + 1u - k; b < x + k && ok;) {
+                const uint64_t w = b >> 6, sh = b & 63u;
+                const uint64_t span = (64u - sh < x + k - b) ? 64u - sh : x + k - b;
+                const uint64_t m = span == 64u ? ~0ull : ((1ull << span) - 1ull);
+                ok = ((tbad[w] >> sh) & m) == 0;
+                b += span;
+            }
+        auto kmer_at = [&](uint64_t pos, uint64_t(&w)[4]) {  // the k bases from pos, words past them zero
+            ax_text_words<4>(t2, pos, w);
+#pragma unroll
+            for (uint32_t c = 0; c < 4u; ++c) {
+                if (k <= 32u * c) w[c] = 0;
+                else if (k < 32u * c + 32u) w[c] &= (1ull << (2u * (k - 32u * c))) - 1ull;
+            }
+        };
+        for (uint32_t i = 0; i < k && ok; ++i) {
+            uint64_t w[4];
+            kmer_at(x + 1u - k + i, w);
+            const uint32_t d = k - 1u - i;  // x's base in this window
+            for (uint64_t sub = 1; sub <= 3u && ok; ++sub) {  // XOR with 1, 2, 3: the three other bases
+                uint64_t v[4];
+#pragma unroll
+                for (uint32_t c = 0; c < 4u; ++c) v[c] = w[c] ^ ((d >> 5) == c ? sub << (2u * (d & 31u)) : 0ull);
+                const uint64_t h = ax_hash<4>(v, k);
+                const uint64_t bits = ax_fbits(h);
+                if ((filt[ax_fword(h, nf)] & bits) != bits) continue;  // absent
+                const uint32_t fp = ax_fp(h);
+                uint32_t b = ax_bucket(h, nb);
+                bool absent = false;
+                for (uint64_t step = 0; step < nb && !absent && ok; ++step) {  // (a chain never wraps a table at
+                    for (uint32_t sl = 0; sl < 8u && !absent && ok; ++sl) {    // its load factor; if it did: 0)
+                        const unsigned long long e = atab[(uint64_t)b * 8u + sl];
+                        if (e == AX_SLOT_EMPTY) {
+                            absent = true;
+                        } else if ((uint32_t)(e >> 48) == fp) {
+                            uint64_t t[4];
+                            kmer_at((uint32_t)e, t);
+                            if (t[0] == v[0] && t[1] == v[1] && t[2] == v[2] && t[3] == v[3]) ok = false;  // occurs
+                        }
+                    }
+                    b = (b + 1u == nb) ? 0u : b + 1u;
+                }
+                if (!absent) ok = false;
+            }
+        }
+        const unsigned long long m = __ballot(ok);
+        if ((threadIdx.x & 63u) == 0u) S[x >> 6] = m;
+    }
+}
+
 // m of the m-mer filter of a text of n symbols for k-mers: the smallest m >= 12 with 4^m >= 200 n (a random m-mer
 // then occurs in the text with probability <= 1 %, so an m-mer over a sequencing error is almost always absent),
 // and only when one probe covers at least AX_MP_COVER windows (k - m + 1): a probe iteration delays its lane by one
@@ -298,7 +364,10 @@ static uint32_t ax_mproof_m(uint64_t n, uint32_t k) {
 // coalesced staging of their next pieces) instead of idling until the wave's slowest read is done. Deferred windows
 // (phase 2) are resolved by the whole wave when SPEQ_AX_BLOCKED finished lanes wait for theirs (their slots hold the
 // bases the deferred entries refer to) or when the list fills up.
-template <int MODE, bool PAIRED, bool LDS_HIST, bool EM, int HW, bool STATS>
+// SP: the substitution proofs (lane state 7) are compiled in: instantiated for HW = 1 only and launched
+// only when the scan uses them, so every other scan runs the kernel without their code (with it compiled in but
+// unused, k = 70 local ran 1.3-1.8 % slower and k = 31 0.3-0.8 %: profiles/r07/ab_lines_unsplit.jsonl)
+template <int MODE, bool PAIRED, bool LDS_HIST, bool EM, int HW, bool STATS, bool SP>
 __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) void k_scan_ax(AxView A, UnitSrc src,
                                                                                   unsigned long long* __restrict__ out_a,
                                                                                   double* __restrict__ out_w) {
@@ -358,9 +427,13 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
     // nothing to load gets an out-of-range offset, which issues no memory request
     const __amdgpu_buffer_rsrc_t rs_gran =
         __builtin_amdgcn_make_buffer_rsrc((void*)A.gran, (short)0, (int)(uint32_t)A.gran_bytes, 0x00020000);
-    // (the anchor table's descriptor also covers the m-mer filter after it: 16-B loads of its 8-B words)
+    // (the anchor table's descriptor also covers the m-mer filter after it: 16-B loads of its 8-B words; and the
+    // substitution bitmap after that)
     const __amdgpu_buffer_rsrc_t rs_atab = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)A.atab, (short)0, (int)(uint32_t)(A.nb * 64u + (A.m != 0u ? A.nmf * 8u + 16u : 0u)), 0x00020000);
+        (void*)A.atab, (short)0,
+        (int)(uint32_t)((SPEQ_AX_SPROOF && SP && A.s_bytes != 0u) ? A.s_off + A.s_bytes
+                                                             : A.nb * 64u + (A.m != 0u ? A.nmf * 8u + 16u : 0u)),
+        0x00020000);
     const __amdgpu_buffer_rsrc_t rs_filt =
         __builtin_amdgcn_make_buffer_rsrc((void*)A.filt, (short)0, (int)(uint32_t)(A.nf * 8u), 0x00020000);
     const uint64_t NWV = (uint64_t)gridDim.x * AX_WPB;
@@ -374,7 +447,7 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
     // diagnostic counters (STATS only; wave-level ones are counted by lane 0)
     uint32_t s_iter = 0, s_lk = 0, s_rn = 0, s_lkw = 0, s_rnw = 0, s_rwin = 0, s_def = 0, s_fp = 0, s_p2 = 0,
              s_p2v = 0, s_ch = 0, s_seg = 0, s_qb = 0, s_tal = 0, s_rg = 0, s_spl = 0, s_b4 = 0, s_b16 = 0, s_b32 = 0,
-             s_b64 = 0, s_p2n = 0, s_p2r = 0;
+             s_b64 = 0, s_p2n = 0, s_p2r = 0, s_spp = 0, s_spw = 0, s_spt = 0;
     // section clocks (STATS only; wave-uniform, kept by every lane, reported by lane 0)
     uint64_t c_ref = 0, c_lk = 0, c_rn = 0, c_p2 = 0, c_p2f = 0, c_rpre = 0, c_rstg = 0, c_t0 = STATS ? clock64() : 0ull, c_s = 0;
 
@@ -560,8 +633,13 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                                // 4: window j is absent and the windows [j + 1, last_mm] share its mismatch last_mm:
                                // probe the m-mers over it, defer the windows no absent m-mer covers (MPROOF),
                                // 5: the same for the windows [j, last_mm] of a speculative run, which then resumes,
-                               // 6: window j is absent, its mismatch unknown: m-mer probes spread over window j
-    bool verify = false;       // st 1: p came from the anchor table (window j itself not compared yet)
+                               // 6: window j is absent, its mismatch unknown: m-mer probes spread over window j,
+                               // 7: window j is absent, its mismatch last_mm known, and p is still the text position
+                               // of window last_mm - k + 1 (verify): probe the substitution bitmap at the mismatch's text
+                               // position p + k - 1 (SPROOF)
+    bool verify = false;       // st 1: p came from the anchor table (window j itself not compared yet); (SPROOF) in
+                               // the lookup states: p is still the text position of window last_mm - k + 1 (set
+                               // with last_mm by the run that broke, unset when p takes a candidate's position)
     uint32_t p = 0;            // text position of window j (st 1)
     uint32_t gt = 0;           // group of p's text (st 1)
     int32_t last_mm = -1;      // base (relative to the piece) of the last observed mismatch
@@ -578,13 +656,24 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
     // its anchor's text: an END window among the pending ones defers them instead.
     constexpr bool SPEC = HW >= SPEQ_AX_SPEC_HW && !EM && MODE == KM_LOCAL;
     constexpr uint32_t AX_PS_SPEC = 16u, AX_PS_FRESH = 17u;
+    // Substitution proofs (SPROOF): a run that breaks at read base e against text position x leaves
+    // window e - k + 1, the first over e, to be looked up; when that finds nothing and S[x] is set (state 7), every
+    // window over e equals the text except at x as far as the read goes on equal to the text after e, and no k-mer
+    // of the texts is a text window with another base at x: the lane neither defers the windows e - k + 2 .. e nor
+    // looks window e + 1 up, it runs on from window e + 1 at text position x + 1 with its first k bases still to be
+    // compared (ps = AX_PS_SFRESH). Matching m bases proves the windows up to e + m - k + 1; a second mismatch within
+    // k - 1 bases defers the windows after that up to e (both mismatches in them), as the lookup path would have.
+    constexpr bool SPROOF = SPEQ_AX_SPROOF != 0 && SP;
+    constexpr uint32_t AX_PS_SFRESH = 18u;
     // (state 6, unknown mismatches, where no speculative run finds them: compiled into those instantiations only —
     // in the speculative ones its code alone cost k = 70 local 31 %, profiles/r05/ab_mtiles_codegen.jsonl)
     constexpr bool MTILES = SPEQ_AX_MTILES && !SPEC;
     uint32_t sp = 0;  // pending windows [sp, sp + k - 2] of the piece; 0: none
     // defers the valid windows of [lo, hi] (hi - lo <= 127; hi < lo: none) of this lane's piece; when the list has
     // no room: the reserved slots are voided, the lane waits for the deferred-window pass (st 3) and false
-    auto defer_except = [&](uint32_t lo, uint32_t hi, uint64_t x0, uint64_t x1) -> bool {  // (x: windows lo + i
+    // (always inlined: as a call, its captured lane state lives in scratch)
+    auto defer_except = [&](uint32_t lo, uint32_t hi, uint64_t x0, uint64_t x1)
+                            __attribute__((always_inline)) -> bool {  // (x: windows lo + i
         if (hi + 1u <= lo) return true;                                                    // proven absent)
         const uint32_t span = hi + 1u - lo;
         uint64_t dm0 = vbits(lane, lo) & ~x0, dm1 = span > 64u ? (vbits(lane, lo + 64u) & ~x1) : 0ull;
@@ -607,7 +696,9 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
         if (STATS) s_def += cnt;
         return true;
     };
-    auto defer_range = [&](uint32_t lo, uint32_t hi) -> bool { return defer_except(lo, hi, 0ull, 0ull); };
+    auto defer_range = [&](uint32_t lo, uint32_t hi) __attribute__((always_inline)) -> bool {
+        return defer_except(lo, hi, 0ull, 0ull);
+    };
 
     auto start_read_at = [&](uint64_t r, uint64_t b, uint64_t e) {  // read r spans [b, e) of seq / qual
         rd = (uint32_t)r;
@@ -1074,7 +1165,9 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
             // when its filter bits are missing those windows are absent. The probes' filter words are loaded by the
             // same four instructions as a bucket (lanes in state 4 never load one); mb[t]: bit indices, bit 31 = used
             // (state 5: the windows j .. e of a speculative run, lo = j, then the run resumes)
-            const bool mk = SPEQ_AX_MPROOF && st >= 4u;
+            const bool sprobe = SPROOF && st == 7u;  // (state 7) the word of S that holds bit p + k - 1, by load 0
+            if (SPROOF && sprobe) o0 = A.s_off + ((p + k - 1u) >> 5) * 4u;
+            const bool mk = SPEQ_AX_MPROOF && st >= 4u && !sprobe;
             const uint32_t km = k - A.m;
             uint32_t mb[AX_MP] = {0u, 0u, 0u, 0u};
             static_assert(AX_MP == 4, "one m-mer probe per bucket load");
@@ -1154,6 +1247,38 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                     last_mm = -1;
                 }
             }
+            if (SPROOF && sprobe) {
+                const uint32_t e1 = (uint32_t)last_mm, dend = min(e1, wend - 1u);
+                if (STATS) s_spp += 1u;
+                if ((q0[0] >> ((p + k - 1u) & 31u)) & 1u) {
+                    // proven, as far as the read goes on equal to the text: run on from window e1 + 1, fresh (past
+                    // the piece's last window too: the bases up to the piece's end still decide)
+                    if (STATS) {
+                        const uint32_t lo = e1 + 2u - k, sp_n = dend + 1u - lo;  // (dend + 1 >= lo; <= k - 1 windows)
+                        if (dend + 1u > lo) {
+                            uint64_t v0 = vbits(lane, lo), v1 = sp_n > 64u ? vbits(lane, lo + 64u) : 0ull;
+                            v0 &= sp_n >= 64u ? ~0ull : ((1ull << sp_n) - 1ull);
+                            if (sp_n > 64u) v1 &= sp_n - 64u >= 64u ? ~0ull : ((1ull << (sp_n - 64u)) - 1ull);
+                            s_spw += (uint32_t)__popcll(v0) + (uint32_t)__popcll(v1);
+                        }
+                    }
+                    j = e1 + 1u;
+                    p += k;
+                    verify = true;
+                    resume = false;
+                    ps = AX_PS_SFRESH;
+                    last_mm = -1;
+                    st = j < wend + k - 1u ? 1u : 2u;  // (the mismatch was the piece's last base: all proven)
+                } else if (SPEQ_AX_MPROOF && A.m != 0u && dend > j) {
+                    st = 4u;  // (a SNP site, a text end, an N) the m-mer probes next, else the deferral, as without S
+                } else {
+                    st = 0u;
+                    if (defer_range(j + 1u, dend)) {  // (no room: st 3, then window j is looked up and S probed again)
+                        j = dend + 1u;
+                        last_mm = -1;
+                    }
+                }
+            }
             if (lk) {
                 uint32_t slot = 0, cp = 0, cg = 0;
                 const uint32_t res = ax_resolve(q0, q1, q2, q3, fp, ps, slot, cp, cg);
@@ -1193,7 +1318,9 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                         dend = min(dend, wend - 1u);
                         // (no room: the lane waits for the deferred-window pass, st 3, and looks window j up again
                         // afterwards — one wasted lookup instead of looking up all k - 1 windows one by one)
-                        if (SPEQ_AX_MPROOF && A.m != 0u && dend > j) {
+                        if (SPROOF && A.s_bytes != 0u && known && verify) {
+                            st = 7u;  // the substitution bitmap decides in the next lookup iteration
+                        } else if (SPEQ_AX_MPROOF && A.m != 0u && dend > j) {
                             st = known ? 4u : ((MTILES && A.mtiles) ? 6u : 0u);  // probes next lookup
                             if (st == 0u && defer_range(j + 1u, dend)) {
                                 j = dend + 1u;
@@ -1308,10 +1435,55 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                     resume = false;
                     ps = 0;
                     last_mm = (int32_t)(j + e);
+                    if (SPROOF) verify = false;
+                } else if (SPROOF && verify && e < k && ps == AX_PS_SFRESH) {
+                    // (SPROOF) the run from window j = e1 + 1 after a proven mismatch e1 matched e < k bases. No
+                    // mismatch (e = cl: the piece ends, j >= wend): every window over e1 is proven. A mismatch at base
+                    // j + e: the windows up to j + e - k are proven; those after, up to e1, hold both mismatches and
+                    // are deferred; window j is then looked up as after any run that broke (e = k - 1: p is still the
+                    // position of the first window over the new mismatch)
+                    const bool mism = e < cl;
+                    const uint32_t lo = j + e + 1u - k, hi = min(j, wend) - 1u;
+                    uint32_t nback = 0;  // (STATS) the valid windows of [lo, hi]: no longer dropped
+                    if (STATS && mism && e + 1u < k && hi + 1u > lo) {
+                        const uint32_t sp_n = hi + 1u - lo;
+                        uint64_t v0 = vbits(lane, lo), v1 = sp_n > 64u ? vbits(lane, lo + 64u) : 0ull;
+                        v0 &= sp_n >= 64u ? ~0ull : ((1ull << sp_n) - 1ull);
+                        if (sp_n > 64u) v1 &= sp_n - 64u >= 64u ? ~0ull : ((1ull << (sp_n - 64u)) - 1ull);
+                        nback = (uint32_t)__popcll(v0) + (uint32_t)__popcll(v1);
+                    }
+                    verify = false;
+                    resume = false;
+                    ps = 0;
+                    if (!mism || e + 1u >= k || defer_range(lo, hi)) {
+                        if (STATS && mism && e + 1u < k) {
+                            s_spt += 1u;
+                            s_spw -= nback;
+                        }
+                        if (mism) {
+                            last_mm = (int32_t)(j + e);
+                            verify = e + 1u == k;
+                        }
+                        st = (mism && j < wend) ? 0u : 2u;
+                    } else {
+                        // no room (st 3): back to the first window over e1, which is looked up again after the
+                        // deferred-window pass and then takes the lookup path (verify unset)
+                        if (STATS) {
+                            const uint32_t l0 = j + 1u - k, h0 = min(j, wend) - 1u, n0 = h0 + 1u - l0;
+                            uint64_t v0 = vbits(lane, l0), v1 = n0 > 64u ? vbits(lane, l0 + 64u) : 0ull;
+                            v0 &= n0 >= 64u ? ~0ull : ((1ull << n0) - 1ull);
+                            if (n0 > 64u) v1 &= n0 - 64u >= 64u ? ~0ull : ((1ull << (n0 - 64u)) - 1ull);
+                            s_spw -= (uint32_t)__popcll(v0) + (uint32_t)__popcll(v1);
+                        }
+                        j -= k;
+                        p -= k;
+                        last_mm = (int32_t)(j + k - 1u);
+                    }
                 } else if (verify && e < k) {  // fingerprint collision: resume probing after that slot
                     st = 0u;
                     resume = true;
                     ++ps;
+                    if (SPROOF) verify = false;  // (p is the candidate's position now)
                 } else {
                     uint32_t R = e - (k - 1u);  // e >= k - 1: a candidate matched k bases, a run k - 1
                     R = min(R, wend - j);
@@ -1439,7 +1611,10 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                         }
                     } else {
                         const bool mism = e < cl;  // the run ended at a mismatch (base j + e)
-                        if (mism && R < wend - j) last_mm = (int32_t)(j + e);
+                        if (mism && R < wend - j) {
+                            last_mm = (int32_t)(j + e);
+                            if (SPROOF) verify = true;  // (p + R below: the position of window j + R = j + e - k + 1)
+                        }
                         j += R;
                         p += R;
                         st = (mism || R == 0u) ? 0u : 1u;
@@ -1530,7 +1705,7 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                                     lane == 0 ? c_p2 : 0ull, lane == 0 ? c_tot : 0ull, s_p2n,
                                     lane == 0 ? c_p2f : 0ull, s_p2r, lane == 0 ? c_rpre : 0ull,
                                     lane == 0 ? c_rstg : 0ull, 0ull, lane == 0 ? 1ull : 0ull, 0ull, 0ull, 0ull, 0ull,
-                                    0ull};
+                                    0ull, s_spp, s_spw, s_spt};
 #pragma unroll
         for (uint32_t i = 0; i < AXS_N; ++i)
             if (sv[i]) atomicAdd(&A.stats[i], (unsigned long long)sv[i]);
@@ -1564,11 +1739,11 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
     }
 }
 
-template <int MODE, bool PAIRED, bool LDS, bool EM, int HW, bool STATS>
+template <int MODE, bool PAIRED, bool LDS, bool EM, int HW, bool STATS, bool SP = false>
 void ax_launch_one(const AxView& A, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st,
                    unsigned long long* a, double* w, uint32_t n_cus) {
     if (lds > 64 * 1024)  // dynamic LDS above 64 KiB must be allowed (occupancy caps pad it)
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan_ax<MODE, PAIRED, LDS, EM, HW, STATS>),
+        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan_ax<MODE, PAIRED, LDS, EM, HW, STATS, SP>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     // persistent waves: at most the blocks that are resident at once (each wave then takes several groups of units
     // and refills its lanes from them)
@@ -1581,14 +1756,14 @@ void ax_launch_one(const AxView& A, const UnitSrc& src, uint32_t grid, size_t ld
         if (cached_lds != lds || cached_blocks == 0) {
             int nb = 0;
             HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                &nb, reinterpret_cast<const void*>(&k_scan_ax<MODE, PAIRED, LDS, EM, HW, STATS>), AX_THREADS, lds));
+                &nb, reinterpret_cast<const void*>(&k_scan_ax<MODE, PAIRED, LDS, EM, HW, STATS, SP>), AX_THREADS, lds));
             cached_lds = lds;
             cached_blocks = std::max(nb, 1);
         }
         per_cu = cached_blocks;
     }
     grid = std::min<uint32_t>(grid, (uint32_t)per_cu * n_cus);
-    hipLaunchKernelGGL((k_scan_ax<MODE, PAIRED, LDS, EM, HW, STATS>), dim3(grid), dim3(AX_THREADS), lds, st, A, src,
+    hipLaunchKernelGGL((k_scan_ax<MODE, PAIRED, LDS, EM, HW, STATS, SP>), dim3(grid), dim3(AX_THREADS), lds, st, A, src,
                        a, w);
 }
 
@@ -1596,7 +1771,9 @@ void ax_launch_one(const AxView& A, const UnitSrc& src, uint32_t grid, size_t ld
 template <int MODE, bool PAIRED, bool LDS, bool EM, bool STATS>
 void ax_launch_nwc(uint32_t k, const AxView& A, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st,
                    unsigned long long* a, double* w, uint32_t n_cus) {
-    if (k <= 32) ax_launch_one<MODE, PAIRED, LDS, EM, 1, STATS>(A, src, grid, lds, st, a, w, n_cus);
+    if (k <= 32 && SPEQ_AX_SPROOF && A.s_bytes != 0u)
+        ax_launch_one<MODE, PAIRED, LDS, EM, 1, STATS, SPEQ_AX_SPROOF != 0>(A, src, grid, lds, st, a, w, n_cus);
+    else if (k <= 32) ax_launch_one<MODE, PAIRED, LDS, EM, 1, STATS>(A, src, grid, lds, st, a, w, n_cus);
     else if (k <= 64) ax_launch_one<MODE, PAIRED, LDS, EM, 2, STATS>(A, src, grid, lds, st, a, w, n_cus);
     else if (k <= 96) ax_launch_one<MODE, PAIRED, LDS, EM, 3, STATS>(A, src, grid, lds, st, a, w, n_cus);
     else ax_launch_one<MODE, PAIRED, LDS, EM, 4, STATS>(A, src, grid, lds, st, a, w, n_cus);
@@ -1734,8 +1911,14 @@ AxTable build_ax(speq_device_index* d, uint32_t k) {
             for (void* q : mine) (void)hipFree(q);
             return AxTable{};
         }
+        // the substitution bitmap S (k_ax_sbitmap, filled by ensure_ax_sproof) after the m-mer filter: 1 bit per text
+        // position in whole blocks of 256, + 16 B of load slack; all zero (no proofs) until it is filled
+        ax.s_off = ax.nb * 64u + (ax.m ? ax.nmf * 8u + 16u : 0u);
+        ax.s_words = SPEQ_AX_SPROOF ? ((n + 255) / 256) * 4 : 0;
+        if (ax.s_off + ax.s_words * 8u + 16u >= (1ull << 32) - 64) ax.s_words = 0;
+        const uint64_t s_bytes = ax.s_words ? ax.s_words * 8u + 16u : 0u;
         HIP_OK(hipMemGetInfo(&free_b, &total_b));
-        const uint64_t atab_bytes = ax.nb * 64u + (ax.m ? ax.nmf * 8u + 16u : 0u);
+        const uint64_t atab_bytes = ax.s_off + s_bytes;
         if (atab_bytes + ax.nf * 8 > free_b / 10 * 9) {  // the table and filters do not fit now: try again later
             cleanup();
             for (void* q : mine) (void)hipFree(q);
@@ -1747,6 +1930,7 @@ AxTable build_ax(speq_device_index* d, uint32_t k) {
         HIP_OK(hipMemsetAsync(ax.filt, 0, ax.nf * 8, d->stream));
         alloc(&ax.atab, atab_bytes);
         HIP_OK(hipMemsetAsync(ax.atab, 0xFF, ax.nb * 64u, d->stream));
+        if (s_bytes) HIP_OK(hipMemsetAsync(static_cast<char*>(ax.atab) + ax.s_off, 0, s_bytes, d->stream));
         if (ax.m) {
             unsigned long long* mf = reinterpret_cast<unsigned long long*>(static_cast<char*>(ax.atab) + ax.nb * 64u);
             HIP_OK(hipMemsetAsync(mf, 0, ax.nmf * 8u + 16u, d->stream));
@@ -1818,6 +2002,36 @@ static bool ensure_ax_em(speq_device_index* d, AxTable* ax, uint32_t k) {
     return true;
 }
 
+// Whether scans with table ax prove the windows over a known mismatch from the substitution bitmap: tuning "ax_sproof"
+// 1, or 2 (the default) where the table has no m-mer filter (k - m + 1 < AX_MP_COVER: the m-mer proofs are unused);
+// k <= 32 only: every longer k has an m-mer filter, against which the bitmap lost 2-5 %, so the
+// kernels of k > 32 are compiled without the path
+bool ax_sproof_on(const speq_device_index* d, const AxTable& ax, uint32_t k) {
+    return SPEQ_AX_SPROOF && k <= 32u && ax.s_words != 0 && (d->ax_sproof == 1u || (d->ax_sproof == 2u && ax.m == 0u));
+}
+
+// Fills the substitution bitmap of table ax (k) once: by speq_device_prepare where the scans of k use it, else by the
+// first scan that does (3 k probes per text position: not paid by the k that never read it). Blocking, on the
+// replica's stream. Returns false when the table has no room for it under its 32-bit buffer offsets.
+bool ensure_ax_sproof(speq_device_index* d, AxTable* ax, uint32_t k) {
+    std::lock_guard<std::mutex> lk(d->ax_mu);
+    if (ax->s_ready) return true;
+    if (ax->s_words == 0) return false;
+    DeviceGuard g(d->device);
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(ax->s_words * 64u / 256u, 65536);
+    hipLaunchKernelGGL(k_ax_sbitmap, dim3(grid), dim3(256), 0, d->stream, d->d_text2, d->d_tbad, (uint64_t)d->view.n, k,
+                       reinterpret_cast<const unsigned long long*>(ax->atab), ax->nb,
+                       reinterpret_cast<const unsigned long long*>(ax->filt), ax->nf,
+                       reinterpret_cast<unsigned long long*>(static_cast<char*>(ax->atab) + ax->s_off), ax->s_words);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(d->stream));
+    ax->s_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ax->build_ms += ax->s_build_ms;
+    ax->s_ready = true;  // last: the unlocked check in launch_ax reads it
+    return true;
+}
+
 // Launches k_scan_ax for a read scan (mode 0 global, 1 local) when replica d has (or can build) the structures of
 // src.k; returns false when the caller must use another kernel. With src.ax_stats set (speq_scan_reads_device_stats:
 // a per-call buffer, so concurrent ordinary scans of the replica never see it), the diagnostic instantiation also adds
@@ -1843,6 +2057,9 @@ bool launch_ax(speq_device_index* d, int mode, bool paired, const UnitSrc& src, 
     A.mtiles = d->ax_mproof == 1u ? 1u : 0u;
     A.nmf = A.m ? ax->nmf : 0u;
     A.mf_off = (uint32_t)(ax->nb * 64u);
+    const bool sproof = ax_sproof_on(d, *ax, src.k) && (ax->s_ready || ensure_ax_sproof(d, ax, src.k));
+    A.s_off = (uint32_t)ax->s_off;
+    A.s_bytes = sproof ? (uint32_t)(ax->s_words * 8u + 16u) : 0u;
     A.G = d->G;
     const bool lds_hist = d->G <= LDS_HIST_MAX_G;
     const uint32_t hist_words = lds_hist ? (mode == KM_GLOBAL ? d->G : 2u * d->G) : 0u;

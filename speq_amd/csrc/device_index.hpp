@@ -29,6 +29,10 @@ struct AxTable {
     uint64_t nf = 0;           // filter words
     uint64_t nmf = 0;          // m-mer filter words (after the nb buckets in atab's allocation; 0: none)
     uint32_t m = 0;            // m of the m-mer filter (0: none)
+    uint64_t s_off = 0;        // byte offset in atab's allocation of the substitution bitmap S (1 bit per text position,
+    uint64_t s_words = 0;      // s_words 64-bit words + 16 B; after the m-mer filter); s_words 0: no room under the
+    bool s_ready = false;      // 32-bit buffer offsets. Filled by ensure_ax_sproof (prepare, or the first scan that uses it)
+    double s_build_ms = 0.0;
     uint64_t gran_bytes = 0;
     uint64_t distinct = 0;     // distinct k-mers of the texts
     uint64_t bytes = 0;        // device bytes of the structures
@@ -103,6 +107,8 @@ struct speq_device_index {
     bool ax_scan = true;            // tuning "ax_scan": read scans of k <= 128 use k_scan_ax
     uint32_t ax_mproof = 1;         // tuning "ax_mproof": m-mer absence proofs for the windows around a mismatch
                                     // (1: known and unknown mismatches, 2: known ones only, 0: off)
+    uint32_t ax_sproof = 2;         // tuning "ax_sproof": substitution-bitmap proofs of the windows over a known mismatch
+                                    // (1: on, 0: off, 2: on where the k's structures have no m-mer filter)
     uint32_t ax_load = 0;           // tuning "ax_load": anchor-table load factor, percent (0: default 35)
     uint32_t grid_blocks_ax = 65535;  // tuning "grid_blocks_ax"
     uint32_t blocks_per_cu_ax = 0;  // tuning "blocks_per_cu_ax" (0: as many as registers/LDS allow)
@@ -124,6 +130,8 @@ DevView search_view(const speq_device_index* d, uint32_t k);  // the FM view a s
 AxTable build_ax(speq_device_index* d, uint32_t k);
 const AxTable* ensure_ax(speq_device_index* d, uint32_t k);
 uint32_t ax_effective_load(const speq_device_index* d);  // the anchor table's load factor (percent) builds use
+bool ax_sproof_on(const speq_device_index* d, const AxTable& ax, uint32_t k);  // tuning "ax_sproof" applied to k
+bool ensure_ax_sproof(speq_device_index* d, AxTable* ax, uint32_t k);  // fills the substitution bitmap (once per k)
 bool launch_ax(speq_device_index* d, int mode, bool paired, const speq_dev::UnitSrc& src, hipStream_t st,
                unsigned long long* a, double* w);
 }  // namespace speq

@@ -2134,6 +2134,8 @@ int speq_device_prepare(speq_device_index* d, uint32_t k, uint64_t* distinct_kme
         if (!d) throw std::invalid_argument("speq_device_prepare: null handle");
         if (k < 1 || k > MAX_K) throw std::invalid_argument("speq_device_prepare: k must be in [1, 4096]");
         if (const speq::AxTable* ax = speq::ensure_ax(d, k)) {  // the read scans' structures for k
+            // (with the substitution bitmap where the scans of k use it: its time and bytes are in the table's)
+            if (speq::ax_sproof_on(d, *ax, k)) (void)speq::ensure_ax_sproof(d, const_cast<speq::AxTable*>(ax), k);
             if (distinct_kmers) *distinct_kmers = ax->distinct;
             if (table_bytes) *table_bytes = ax->bytes;
             if (build_ms) *build_ms = ax->build_ms;
@@ -2143,6 +2145,19 @@ int speq_device_prepare(speq_device_index* d, uint32_t k, uint64_t* distinct_kme
         if (distinct_kmers) *distinct_kmers = kt ? kt->distinct : 0;
         if (table_bytes) *table_bytes = kt ? kt->bytes : 0;
         if (build_ms) *build_ms = kt ? kt->build_ms : 0.0;
+    });
+}
+
+int speq_device_sproof_bitmap(speq_device_index* d, uint32_t k, uint64_t* words, uint64_t n_words) {
+    return speq::guarded([&] {
+        if (!d || !words) throw std::invalid_argument("speq_device_sproof_bitmap: null argument");
+        speq::AxTable* ax = const_cast<speq::AxTable*>(speq::ensure_ax(d, k));
+        if (!ax || !speq::ensure_ax_sproof(d, ax, k))
+            throw std::invalid_argument("speq_device_sproof_bitmap: no anchor structures / bitmap for this k");
+        const uint64_t need = (d->view.n + 63) / 64;
+        if (n_words < need) throw std::invalid_argument("speq_device_sproof_bitmap: n_words < ceil(n / 64)");
+        DeviceGuard g(d->device);
+        HIP_OK(hipMemcpy(words, static_cast<const char*>(ax->atab) + ax->s_off, need * 8, hipMemcpyDeviceToHost));
     });
 }
 
@@ -2197,6 +2212,9 @@ int speq_device_set_tuning(speq_device_index* d, const char* key, int64_t value)
         } else if (k == "ax_mproof") {
             if (value < 0 || value > 2) throw std::invalid_argument("ax_mproof must be 0, 1 or 2");
             d->ax_mproof = (uint32_t)value;
+        } else if (k == "ax_sproof") {
+            if (value < 0 || value > 2) throw std::invalid_argument("ax_sproof must be 0, 1 or 2");
+            d->ax_sproof = (uint32_t)value;
         } else if (k == "ax_load") {
             if (value < 10 || value > 90) throw std::invalid_argument("ax_load must be in [10, 90] (percent)");
             std::lock_guard<std::mutex> lk(d->ax_mu);
@@ -2251,6 +2269,7 @@ int speq_device_get_tuning(const speq_device_index* d, const char* key, int64_t*
         else if (k == "ax_scan") *value = d->ax_scan ? 1 : 0;
         else if (k == "last_kernel") *value = d->last_kernel;
         else if (k == "ax_mproof") *value = d->ax_mproof;
+        else if (k == "ax_sproof") *value = d->ax_sproof;
         else if (k == "ax_load") *value = speq::ax_effective_load(d);
         else if (k == "grid_blocks_ax") *value = d->grid_blocks_ax;
         else if (k == "blocks_per_cu_ax") *value = d->blocks_per_cu_ax;
