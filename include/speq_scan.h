@@ -224,6 +224,12 @@ int speq_em_scan_reads_device(speq_em* em, const uint8_t* d_seq, const uint8_t* 
 int speq_em_finalize(speq_em* em, uint32_t threads);
 /* Distinct intervals recorded, their (group, count) entries, and the windows (sum of multiplicities); before merging. */
 int speq_em_info(const speq_em* em, uint64_t* n_intervals, uint64_t* n_entries, uint64_t* n_windows);
+/* Test accessor: the finalized rows as CSR (after merging, so n_rows <= n_intervals and n_entries here counts the
+ * merged rows' entries). Call with null arrays for the sizes, then with row_mult[n_rows], row_ptr[n_rows + 1],
+ * col_group[n_entries], col_count[n_entries] (any may be null) for a copy: row r has multiplicity row_mult[r] and the
+ * entries row_ptr[r] .. row_ptr[r + 1], groups ascending. Fails with SPEQ_E_ARG before speq_em_finalize. */
+int speq_em_rows(const speq_em* em, uint64_t* n_rows, uint64_t* n_entries, uint64_t* row_mult, uint64_t* row_ptr,
+                 uint32_t* col_group, uint32_t* col_count);
 /* next[g] = sum over passing windows with hits of (c_g p_g / n_g) / sum_j (c_j p_j / n_j) (windows with a
  * non-positive sum skipped), given percent[G], group_counts[G] (the "(count)" of each groupings line) and
  * unique[G] (the U[g] counters of the same scan, i.e. its single-group windows). */

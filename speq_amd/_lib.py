@@ -90,6 +90,7 @@ SIGNATURES = {
     "speq_em_scan_reads_device": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.POINTER(ScanParams), _P, _P, _P]),
     "speq_em_finalize": (C.c_int, [_P, C.c_uint32]),
     "speq_em_info": (C.c_int, [_P, _U64P, _U64P, _U64P]),
+    "speq_em_rows": (C.c_int, [_P, _U64P, _U64P, _U64P, _U64P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "speq_em_step": (C.c_int, [_P, _F64P, _I32P, _U64P, _F64P]),
     "speq_em_free": (None, [_P]),
     "speq_pipeline_create": (C.c_int, [_P, C.POINTER(ScanParams), _P, C.c_uint64, C.c_uint64, C.c_uint32,

@@ -458,6 +458,20 @@ class EmHistogram:
         check(lib().speq_em_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def rows(self) -> list[tuple[int, tuple[tuple[int, int], ...]]]:
+        """Test accessor (speq_em_rows): the finalized rows, in order, as (multiplicity, ((group, count), ...))."""
+        nr, ne = C.c_uint64(), C.c_uint64()
+        check(lib().speq_em_rows(self._h, C.byref(nr), C.byref(ne), None, None, None, None))
+        mult = np.zeros(nr.value, dtype=np.uint64)
+        ptr = np.zeros(nr.value + 1, dtype=np.uint64)
+        grp = np.zeros(ne.value, dtype=np.uint32)
+        cnt = np.zeros(ne.value, dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        check(lib().speq_em_rows(self._h, None, None, _u64p(mult), _u64p(ptr), grp.ctypes.data_as(u32p),
+                                 cnt.ctypes.data_as(u32p)))
+        p, g, c = ptr.tolist(), grp.tolist(), cnt.tolist()
+        return [(int(mult[r]), tuple(zip(g[p[r]:p[r + 1]], c[p[r]:p[r + 1]]))) for r in range(nr.value)]
+
     def step(self, percent, group_counts, unique) -> np.ndarray:
         p = np.ascontiguousarray(percent, dtype=np.float64)
         gc = np.ascontiguousarray(group_counts, dtype=np.int32)

@@ -79,16 +79,22 @@ namespace speq {
 // Rows with the same (group, count) entries — k-mers whose occurrences lie in the same texts — contribute the same
 // function of the step's percentages times their multiplicity, so they are merged into the first of them with the
 // multiplicities summed (the sums then differ from row-by-row ones by fp64 re-association only). Row order: first
-// occurrence. SPEQ_EM_MERGE_ROWS=0 keeps every interval's row (A/B).
+// occurrence. SPEQ_EM_MERGE_ROWS=0 keeps every interval's row (A/B); =2 gives every row the same hash, so that the
+// collision fallback below does the merging (tests).
 void merge_equal_rows(speq_em& em) {
     const char* e = std::getenv("SPEQ_EM_MERGE_ROWS");
     const uint64_t R = em.row_mult.size();
     if ((e && e[0] == '0') || R < 2) return;
+    const bool one_hash = e && e[0] == '2';
     std::vector<uint64_t> h(R);
     const uint64_t n_chunks = std::min<uint64_t>(EM_CHUNKS, std::max<uint64_t>(1, R / 2048));
     auto hash_rows = [&](uint64_t ci) {
         for (uint64_t r = R * ci / n_chunks; r < R * (ci + 1) / n_chunks; ++r) {
             uint64_t x = 0x9E3779B97F4A7C15ull ^ (em.row_ptr[r + 1] - em.row_ptr[r]);
+            if (one_hash) {
+                h[r] = 0x9E3779B97F4A7C15ull;
+                continue;
+            }
             for (uint64_t i = em.row_ptr[r]; i < em.row_ptr[r + 1]; ++i) {
                 x ^= ((uint64_t)em.col_group[i] << 32) | em.col_count[i];
                 x *= 0xFF51AFD7ED558CCDull;
@@ -259,6 +265,19 @@ int speq_em_info(const speq_em* em, uint64_t* n_intervals, uint64_t* n_entries, 
             for (uint64_t m : em->row_mult) s += m;
             *n_windows = s;
         }
+    });
+}
+
+int speq_em_rows(const speq_em* em, uint64_t* n_rows, uint64_t* n_entries, uint64_t* row_mult, uint64_t* row_ptr,
+                 uint32_t* col_group, uint32_t* col_count) {
+    return speq::guarded([&] {
+        if (!em || !em->finalized) throw std::invalid_argument("speq_em_rows: histogram not finalized");
+        if (n_rows) *n_rows = em->row_mult.size();
+        if (n_entries) *n_entries = em->col_group.size();
+        if (row_mult) std::copy(em->row_mult.begin(), em->row_mult.end(), row_mult);
+        if (row_ptr) std::copy(em->row_ptr.begin(), em->row_ptr.end(), row_ptr);
+        if (col_group) std::copy(em->col_group.begin(), em->col_group.end(), col_group);
+        if (col_count) std::copy(em->col_count.begin(), em->col_count.end(), col_count);
     });
 }
 

@@ -4,6 +4,7 @@
 import numpy as np
 import pytest
 
+import em_reference
 from golden_io import CASES, Case
 from oracle.oracle import Oracle
 from speq_amd import DeviceIndex, EmHistogram, FmIndex, em_refine, synth, unique_to_percent
@@ -60,8 +61,11 @@ def test_em_step_matches_oracle_larger(paired, label_table):
         for j in range(len(s) - k + 1):
             if q[j:j + k].min() > cutoff and b"N" not in s[j:j + k] and orc.lookup(s[j:j + k]) == -2:
                 multi += 1
-    n_int, n_ent, n_win = em.info()
-    assert n_win == multi and n_int <= n_win and n_ent >= 2 * n_int
+    # ... as that many distinct intervals with that many (group, count) entries (tests/em_reference.py)
+    h = em_reference.scan(em_reference.build_index(ref.records, ref.groups, G, k), G, k, reads.seq, reads.qual,
+                          reads.offsets, cutoff=cutoff, paired=paired)
+    assert h.n_windows == multi
+    assert em.info() == (h.n_intervals, h.n_entries, multi)
     rng = np.random.default_rng(3)
     for percent in (np.full(G, 20.0), rng.uniform(0, 50, G), np.array([0.0, 10.0, 0.0, 5.0, 1.0])):
         got = em.step(percent, counts, r.unique)
