@@ -226,3 +226,54 @@ def test_compact_table_poly_t_and_full_buckets(load8):
         T, amb, U, W = Oracle(recs, groups, 3, k).scan(np.frombuffer(seq, np.uint8), np.frombuffer(qual, np.uint8),
                                                        off, local=True)
         assert res[("compact", k)][:3] == (T, amb, U.tolist())
+
+
+@pytest.mark.parametrize("shared,falls_back", [(70_000, True), (65_000, False)], ids=["over-cap", "under-cap"])
+def test_compact_table_falls_back_when_multi_group_kmers_outgrow_the_payload(shared, falls_back):
+    """A compact slot's payload at k = 23 has 64 - 46 = 18 bits, one of them the multi-group flag: 2^17 - 2 multi-group
+    k-mers at most, beyond which build_ktab drops the compact table and fills 16-B slots. One random sequence shared
+    by two records of two groups gives 2 (shared - 22) multi-group 23-mers: 139,956 (over the cap of 131,070: same
+    bytes as a wide request) and 129,956 (just under: compact, smaller). Each record ends in 2,000 bases of its own,
+    so both groups have unique windows. Counters, W, EM rows and the .dat pass equal the oracle and the LF-step scan;
+    k = 22 (19 payload bits) stays compact on the first reference."""
+    rng = np.random.default_rng(shared)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    common = bytes(rng.choice(acgt, size=shared))
+    recs = [common + bytes(rng.choice(acgt, size=2_000)) for _ in range(2)]
+    groups = [0, 1]
+    assert (2 * (shared - 22) > 2 ** 17 - 2) == falls_back
+    idx = FmIndex.build(recs, groups, 2, prefix_q=8, pair_steps=True, triple_steps=True)
+    reads = synth.make_reads(synth.Reference(recs, groups, 2, 1, len(recs[0])), 4_000, err_rate=0.004, n_rate=0.001)
+    res, size = {}, {}
+    for mode in ("compact", "wide", "lf"):
+        dev = DeviceIndex(idx)
+        dev.tune(kt_compact=int(mode == "compact"), kmer_table=int(mode != "lf"), ax_scan=0)
+        for k in (23, 22) if falls_back else (23,):
+            size[(mode, k)] = dev.prepare(k)["table_bytes"]
+            em = EmHistogram(dev)
+            r = em.scan(reads.seq.tobytes(), reads.qual.tobytes(), reads.offsets, k=k, local=True)
+            em.finalize()
+            u = dev.count_unique_kmers_per_group(k)
+            res[(mode, k)] = (r.total, r.ambiguous, r.unique.tolist(), r.weights, em.info(), em.rows(),
+                              em.step([40.0, 60.0], [1, 1], r.unique), u[0].tolist(), u[1].tolist())
+            em.close()
+        dev.close()
+    for k in (23, 22) if falls_back else (23,):
+        orc = Oracle(recs, groups, 2, k)
+        T, amb, U, W = orc.scan(reads.seq, reads.qual, reads.offsets, local=True)
+        ou, ot = orc.ref_unique()
+        for mode in ("compact", "wide", "lf"):
+            a = res[(mode, k)]
+            assert a[:3] == (T, amb, U.tolist()), (mode, k)
+            np.testing.assert_allclose(a[3], W, rtol=1e-10, atol=0)
+            assert a[7:] == (ou.tolist(), ot.tolist()), (mode, k)
+            b = res[("lf", k)]
+            np.testing.assert_allclose(a[3], b[3], rtol=1e-12)
+            assert a[4] == b[4] and sorted(a[5]) == sorted(b[5]), (mode, k)
+            np.testing.assert_array_equal(a[6], b[6])
+        assert res[("lf", k)][4][0] > 0 and int(U.sum()) > 0  # multi-group rows and unique windows both exist
+    if falls_back:
+        assert size[("compact", 23)] == size[("wide", 23)], size  # the fallback happened
+        assert size[("compact", 22)] < size[("wide", 22)], size   # k = 22 stays compact
+    else:
+        assert size[("compact", 23)] < size[("wide", 23)], size
