@@ -403,6 +403,20 @@ int speq_device_prepare(speq_device_index* d, uint32_t k, uint64_t* distinct_kme
  * SPEQ_E_ARG when the anchor-and-extend scan does not take k. Blocking. */
 int speq_device_sproof_bitmap(speq_device_index* d, uint32_t k, uint64_t* words, uint64_t n_words);
 
+/* Test accessor: one run of the GPU FASTQ parser (fastq_gpu.hip, the parser of speq_scan_fastq's raw blocks) on
+ * `device`. raw (host) holds file 1's four-line text [0, len1) followed, when paired, by file 2's [len1, len1 + len2);
+ * n_records is the record count per file. The text is copied into a 16-byte aligned device buffer of
+ * align16(len1 + len2) + 16 bytes whose remainder is filled with pad_byte; the parser's scratch, the offsets and the
+ * two output buffers (len1 + len2 bytes each) are filled with `poison` first, then the parser is launched as the
+ * stream path launches it. Outputs (host): seq / qual, all len1 + len2 bytes of each, so the bytes at and after
+ * offsets[n_slots] show what the parser left alone; offsets, u64[n_slots + 1] with n_slots = n_records * (paired ? 2
+ * : 1), records interleaved (slot 2r + f) when paired; *err, the OR of the records' flags (1 header not '@', 2
+ * separator line, 4 base / quality counts, 8 too few lines; a flagged record has length 0); *total_bases =
+ * offsets[n_slots] as the stream statistics get it. n_records = 0 launches nothing (offsets[0] = 0). Blocking. */
+int speq_fastq_parse_block(int device, const uint8_t* raw, uint64_t len1, uint64_t len2, uint64_t n_records,
+                           uint32_t paired, uint8_t pad_byte, uint8_t poison, uint8_t* seq, uint8_t* qual,
+                           uint64_t* offsets, uint32_t* err, uint64_t* total_bases);
+
 /* ---- kernel timing (HIP events on the launch stream; bench/roofline support) ----
  * Returns the summed elapsed milliseconds of the scan kernels launched by speq_scan_reads_device on
  * this handle since the last reset, and the number of launches.  Enabled by speq_timing_enable(d, 1). */

@@ -126,6 +126,8 @@ SIGNATURES = {
     "speq_device_get_tuning": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
     "speq_device_prepare": (C.c_int, [_P, C.c_uint32, _U64P, _U64P, _F64P]),
     "speq_device_sproof_bitmap": (C.c_int, [_P, C.c_uint32, _U64P, C.c_uint64]),
+    "speq_fastq_parse_block": (C.c_int, [C.c_int, _P, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint8,
+                                         C.c_uint8, _P, _P, _U64P, C.POINTER(C.c_uint32), _U64P]),
     "speq_timing_enable": (C.c_int, [_P, C.c_int]),
     "speq_timing_read": (C.c_int, [_P, _F64P, _U64P]),
 }

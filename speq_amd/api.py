@@ -40,6 +40,24 @@ def pack_records(records: Sequence[bytes | str]) -> tuple[bytes, np.ndarray]:
     return b"".join(bs), off
 
 
+def fastq_parse_block(raw1: bytes, raw2: Optional[bytes] = None, n_records: int = 0, pad_byte: int = 0x0A,
+                      poison: int = 0, device: int = 0):
+    """Test accessor (speq_fastq_parse_block): one run of the GPU FASTQ parser over file 1's text (and file 2's when
+    raw2 is not None), n_records per file. Returns (seq, qual, offsets, err, total_bases): seq / qual are all
+    len(raw1) + len(raw2) bytes of the output buffers, `poison` wherever the parser wrote nothing."""
+    paired = raw2 is not None
+    raw = bytes(raw1) + (bytes(raw2) if paired else b"")
+    n_slots = n_records * (2 if paired else 1)
+    seq = np.empty(len(raw), dtype=np.uint8)
+    qual = np.empty(len(raw), dtype=np.uint8)
+    off = np.zeros(n_slots + 1, dtype=np.uint64)
+    err, total = C.c_uint32(), C.c_uint64()
+    check(lib().speq_fastq_parse_block(device, raw, len(raw1), len(raw2) if paired else 0, n_records, int(paired),
+                                       pad_byte, poison, seq.ctypes.data, qual.ctypes.data, _u64p(off),
+                                       C.byref(err), C.byref(total)))
+    return seq, qual, off, err.value, total.value
+
+
 @dataclass
 class Groupings:
     names: list[str]

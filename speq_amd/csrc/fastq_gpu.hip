@@ -14,6 +14,7 @@
 #include <cstdint>
 #include <string>
 
+#include "capi_internal.hpp"
 #include "speq_errors.hpp"
 
 namespace speq {
@@ -149,7 +150,9 @@ __global__ __launch_bounds__(256) void k_records(const uint8_t* __restrict__ bas
     // the third line must open with '+', and the second must not (the host grammar would take it as the separator)
     if (p0 >= end || base[p0] != '+' || (s0 < s1 && base[s0] == '+')) e |= ERR_PLUS;
     const uint64_t ns = wave_count<true>(base, s0, se, lane), nq = wave_count<false>(base, q0, qe, lane);
-    if (ns != nq) e |= ERR_LENGTH;
+    // no bases (an empty base line, or one of blanks and digits): the host grammar ends such a record at its '+' line
+    // and takes a quality line that is not empty, blanks included, for the next header: not a four-line record
+    if (ns != nq || (ns == 0 && qe > q0)) e |= ERR_LENGTH;
     if (lane == 0) {
         if (e) atomicOr(err, e);
         lens[slot] = e ? 0 : ns;
@@ -454,6 +457,73 @@ void launch_fastq_parse(const uint8_t* d_raw, uint64_t len1, uint64_t len2, uint
 }
 
 }  // namespace speq
+
+namespace speq {
+namespace {
+struct DevBuf {  // device allocation of at least one byte, freed on scope exit
+    uint8_t* p = nullptr;
+    explicit DevBuf(size_t n) { FHIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 16))); }
+    ~DevBuf() { (void)hipFree(p); }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+};
+struct DevSelect {  // hipSetDevice for the scope
+    int prev = 0;
+    explicit DevSelect(int device) {
+        FHIP(hipGetDevice(&prev));
+        FHIP(hipSetDevice(device));
+    }
+    ~DevSelect() { (void)hipSetDevice(prev); }
+};
+}  // namespace
+}  // namespace speq
+
+extern "C" int speq_fastq_parse_block(int device, const uint8_t* raw, uint64_t len1, uint64_t len2, uint64_t n_records,
+                                      uint32_t paired, uint8_t pad_byte, uint8_t poison, uint8_t* seq, uint8_t* qual,
+                                      uint64_t* offsets, uint32_t* err, uint64_t* total_bases) {
+    return speq::guarded([&] {
+        using namespace speq;
+        if (!offsets || !err || !total_bases) throw std::invalid_argument("speq_fastq_parse_block: null argument");
+        if (device < 0) throw std::invalid_argument("speq_fastq_parse_block: bad device ordinal");
+        if (paired > 1) throw std::invalid_argument("speq_fastq_parse_block: paired must be 0 or 1");
+        if (!paired && len2) throw std::invalid_argument("speq_fastq_parse_block: len2 without paired");
+        if (len1 >= (uint64_t(1) << 32) || len2 >= (uint64_t(1) << 32) || len1 + len2 >= (uint64_t(1) << 32))
+            throw std::invalid_argument("speq_fastq_parse_block: block exceeds 4 GiB");
+        if (n_records >= (uint64_t(1) << 28)) throw std::invalid_argument("speq_fastq_parse_block: too many records");
+        const uint64_t len = len1 + len2;
+        if (len && (!raw || !seq || !qual)) throw std::invalid_argument("speq_fastq_parse_block: null argument");
+        *err = 0;
+        *total_bases = 0;
+        offsets[0] = 0;
+        if (n_records == 0) return;
+        const uint64_t n_slots = n_records * (paired ? 2 : 1);
+        const uint64_t raw_cap = align16(len) + 16;
+        const size_t scratch_bytes = fastq_gpu_scratch_bytes(std::max(len1, len2), n_records, paired != 0);
+        DevSelect g(device);
+        DevBuf d_raw(raw_cap), d_scratch(scratch_bytes), d_seq(len), d_qual(len), d_off((n_slots + 1) * 8), d_misc(32);
+        FHIP(hipMemset(d_raw.p + len, pad_byte, raw_cap - len));
+        if (len) FHIP(hipMemcpy(d_raw.p, raw, len, hipMemcpyHostToDevice));
+        FHIP(hipMemset(d_scratch.p, poison, scratch_bytes));
+        FHIP(hipMemset(d_off.p, poison, (n_slots + 1) * 8));
+        if (len) {
+            FHIP(hipMemset(d_seq.p, poison, len));
+            FHIP(hipMemset(d_qual.p, poison, len));
+        }
+        FHIP(hipMemset(d_misc.p, 0, 32));  // [0, 4) the error flags, [16, 24) the base total
+        FHIP(hipDeviceSynchronize());
+        launch_fastq_parse(d_raw.p, len1, len2, n_records, paired != 0, d_scratch.p, scratch_bytes, d_seq.p, d_qual.p,
+                           reinterpret_cast<uint64_t*>(d_off.p), reinterpret_cast<uint32_t*>(d_misc.p),
+                           reinterpret_cast<uint64_t*>(d_misc.p + 16), nullptr);
+        FHIP(hipDeviceSynchronize());
+        if (len) {
+            FHIP(hipMemcpy(seq, d_seq.p, len, hipMemcpyDeviceToHost));
+            FHIP(hipMemcpy(qual, d_qual.p, len, hipMemcpyDeviceToHost));
+        }
+        FHIP(hipMemcpy(offsets, d_off.p, (n_slots + 1) * 8, hipMemcpyDeviceToHost));
+        FHIP(hipMemcpy(err, d_misc.p, 4, hipMemcpyDeviceToHost));
+        FHIP(hipMemcpy(total_bases, d_misc.p + 16, 8, hipMemcpyDeviceToHost));
+    });
+}
 
 namespace speq {
 // Loads this translation unit's code object onto the current device (HIP loads a code object at the first use of

@@ -325,6 +325,11 @@ inline bool fast_record(const char* data, size_t len, size_t pos, bool eof, size
     };
     const size_t l2 = trimmed(nl[0] + 1, nl[1]), l4 = trimmed(nl[2] + 1, nl[3]);
     if (l2 != l4 || trimmed(pos, nl[0]) == 0) return false;
+    // a base line of blanks and digits only gives no bases, so the general grammar ends the record at the '+' line
+    // and reads the quality line as the next header: not a four-line record (one load when the line opens with a base)
+    size_t first = nl[0] + 1;
+    while (first < nl[0] + 1 + l2 && !is_seq_char((unsigned char)data[first])) ++first;
+    if (l2 && first == nl[0] + 1 + l2) return false;
     end = p;
     seq_len = l2;
     return true;
@@ -1214,7 +1219,14 @@ StreamTotals run_stream(const char* path1, const char* path2, uint32_t threads, 
                             s.offsets[i + 1] = out;
                         }
                     }
-                    // the general grammar must end exactly where the cutter did
+                    // the general grammar must end exactly where the cutter did; the empty quality line of a four-line
+                    // record without bases is a blank line to it, which the next record skips and the last one leaves
+                    auto skip_blank = [](const char* data, size_t len, size_t& pos) {
+                        size_t p = pos, b = 0, e = 0;
+                        while (get_line(data, len, p, true, b, e) && e == b) pos = p;
+                    };
+                    skip_blank(w.b1.data(), w.b1.size(), p1);
+                    if (paired) skip_blank(w.b2.data(), w.b2.size(), p2);
                     if ((w.n == w.b1.n && p1 != w.b1.size()) || (paired && p2 != w.b2.size()))
                         throw IoError(std::string("irregular FASTQ record layout in ") +
                                       (p1 != w.b1.size() ? path1 : path2));

@@ -129,7 +129,7 @@ def test_paired_files_of_unequal_length_zip_to_the_shorter(tmp_path):
     assert st["records"] == 400
 
 
-def test_scan_fastq_errors(tmp_path):
+def test_scan_fastq_errors(tmp_path, monkeypatch):
     ref = synth.make_reference(2, 1, 2_000)
     dev = DeviceIndex(FmIndex.build(ref.records, ref.groups, 2, prefix_q=4))
     (tmp_path / "a.fa").write_text(">r\nACGT\n")
@@ -145,6 +145,17 @@ def test_scan_fastq_errors(tmp_path):
     (tmp_path / "empty.fq").write_text("")
     r, st = dev.scan_fastq(str(tmp_path / "empty.fq"), k=3)
     assert r.total == 0 and st["records"] == 0
+    # a base line of blanks gives no bases: the record ends at its '+' line and the quality line of blanks is read as
+    # the next header, on every path (parallel or sequential cut; parsed on the GPU, on the host, or packed)
+    (tmp_path / "blank.fq").write_text("@a\nACGT\n+\nIIII\n@r\n \n+\n \n@b\nACGT\n+\nIIII\n")
+    for split_cut, gpu, pack in (("1", 1, "0"), ("0", 1, "0"), ("1", 0, "0"), ("0", 0, "0"), ("1", 1, "1"),
+                                 ("0", 1, "1")):
+        monkeypatch.setenv("SPEQ_SPLIT_CUT", split_cut)
+        monkeypatch.setenv("SPEQ_FASTQ_PACK", pack)
+        dev.tune(fastq_gpu_parse=gpu)
+        with pytest.raises(SpeqError, match="malformed FASTQ record header"):
+            dev.scan_fastq(str(tmp_path / "blank.fq"), k=3)
+    dev.tune(fastq_gpu_parse=1)
 
 
 @pytest.mark.parametrize("local", [False, True])
@@ -261,7 +272,7 @@ def test_gpu_fastq_parse_blanks_and_errors(tmp_path):
 
 
 PARALLEL_CASES = ["simple", "wrapped_late", "blank_late", "blank_tail", "crlf", "no_final_newline", "error_late",
-                  "plus_base_line"]
+                  "plus_base_line", "blank_base_line"]
 
 
 @pytest.mark.parametrize("case", PARALLEL_CASES)
@@ -279,7 +290,8 @@ def test_parallel_cut_stream_and_restart(tmp_path, monkeypatch, case):
     data = p.read_bytes()
     cut = data.index(b"\n@read", len(data) * 5 // 6) + 1
     extra = {"wrapped_late": b"@w\nACGTACGTAC\nGTACGTACGT\n+\nIIIIIIIIII\nIIIIIIIIII\n", "blank_late": b"\n",
-             "error_late": b"@e\nACGT\n+\nII\n", "plus_base_line": b"@p\n+ACGT\n+\nIIIII\n"}.get(case)
+             "error_late": b"@e\nACGT\n+\nII\n", "plus_base_line": b"@p\n+ACGT\n+\nIIIII\n",
+             "blank_base_line": b"@p\n \n+\n \n"}.get(case)
     if extra:
         data = data[:cut] + extra + data[cut:]
     if case == "blank_tail":
@@ -288,7 +300,7 @@ def test_parallel_cut_stream_and_restart(tmp_path, monkeypatch, case):
         data = data[:-1]
     p.write_bytes(data)
     dev = DeviceIndex(FmIndex.build(ref.records, ref.groups, 4, prefix_q=10, pair_steps=True, triple_steps=True))
-    if case in ("error_late", "plus_base_line"):
+    if case in ("error_late", "plus_base_line", "blank_base_line"):
         for split_cut in ("1", "0"):
             monkeypatch.setenv("SPEQ_SPLIT_CUT", split_cut)
             with pytest.raises(SpeqError, match="mismatch" if case == "error_late" else "malformed"):
