@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SPEQ_ABI_VERSION 7
+#define SPEQ_ABI_VERSION 8
 
 enum {
     SPEQ_OK = 0,
@@ -172,6 +172,32 @@ int speq_scan_reads_device_stats(speq_device_index* d, const uint8_t* d_seq, con
 int speq_scan_reads(speq_device_index* d, const uint8_t* seq, const uint8_t* qual, const uint64_t* offsets,
                     uint64_t n_reads, const speq_scan_params* params, uint64_t* counts, double* weights);
 
+/* ---- per-unit report (a diagnostic pass beside the scan) ----
+ * A unit is a read, or the pair (2i, 2i+1) when params->paired is set. For every unit: a fixed record and the set of
+ * groups that at least one of its windows is unique to, as W = SPEQ_SET_WORDS(G) u64 words (bit g % 64 of word
+ * g / 64). A unit is ambiguous iff its set holds two or more bits; the number of such units is counts[1] of a scan of
+ * the same reads. Window filter and base conversion are the scan's; params->mode is ignored. Every passing window is
+ * searched exactly (no per-k structure), so this is far slower than the scan: an opt-in pass, not the hot path.
+ * The reference keeps none of this: its paired "fusion map" (fm_scanner.cpp:915-1033) is keyed by a copy of the set
+ * that is always empty (:916). */
+#define SPEQ_REPORT_MAX_K 1024
+typedef struct {
+    uint32_t passing;     /* passing windows of the unit; sum over units == counts[0] of a scan */
+    uint32_t unique;      /* windows whose k-mer occurs in texts of exactly one group; sum == sum of U[g] */
+    uint32_t shared;      /* passing windows whose k-mer occurs in texts of >= 2 groups;
+                             sum == n_windows of the EM histogram */
+    uint32_t first_group; /* group of the first unique window (mate 1 before mate 2, ascending start):
+                             the reference's which_group, fm_scanner.cpp:183-190; 0xFFFFFFFF when none */
+} speq_read_report;       /* 16 bytes */
+#define SPEQ_SET_WORDS(G) (((size_t)(G) + 63u) / 64u)
+/* Device buffers (d_reports 16-byte aligned), asynchronous on stream; overwrites n_units records and n_units * W set
+ * words, nothing else. 1 <= k <= SPEQ_REPORT_MAX_K; reads of any length; n_reads == 0 launches nothing. */
+int speq_report_reads_device(speq_device_index* d, const uint8_t* d_seq, const uint8_t* d_qual,
+                             const uint64_t* d_offsets, uint64_t n_reads, const speq_scan_params* params,
+                             speq_read_report* d_reports, uint64_t* d_sets, void* stream);
+/* Host buffers, synchronous, staged in batches like speq_scan_reads. */
+int speq_report_reads(speq_device_index* d, const uint8_t* seq, const uint8_t* qual, const uint64_t* offsets,
+                      uint64_t n_reads, const speq_scan_params* params, speq_read_report* reports, uint64_t* sets);
 /* ---- reference-uniqueness pass (replaces _async_count_unique_kmers_per_group, fm_scanner.cpp:1476-1576)
  * For every window of every text (fwd and rc of each record): Tot_ref[g] += 1, and U_ref[g] += 1 iff
  * every occurrence lies in a text of group g.  Outputs are host arrays of G u64 (overwritten). */
@@ -287,6 +313,20 @@ int speq_stream_reserve(int device, uint32_t threads, uint32_t paired);
  * order-independent digest = sum over records of mix64(FNV-1a-64 over (len, (base << 8 | qual) per position)). */
 int speq_fastq_checksum(const char* path1, const char* path2, uint32_t threads, uint64_t* records, uint64_t* bases,
                         uint64_t* digest);
+
+/* The per-unit report (speq_report_reads) of FASTQ file(s) as an order-independent summary: one entry per distinct
+ * group set with the number of units that have it, sorted ascending by the set read as one integer (word W-1 most
+ * significant), so the empty set comes first. Entries with two or more bits are the real fusion map. The blocks are
+ * parsed on host threads and reported in any order; stats may be NULL. */
+typedef struct speq_group_sets speq_group_sets;
+int speq_report_fastq(speq_device_index* d, const char* path1, const char* path2, const speq_scan_params* params,
+                      uint32_t threads, speq_group_sets** out, speq_stream_stats* stats);
+uint64_t speq_group_sets_count(const speq_group_sets* s);  /* distinct sets, the empty set included */
+int speq_group_sets_get(const speq_group_sets* s, uint64_t i, uint64_t* words /* W */, uint64_t* units);
+/* Sums over all units (any output may be NULL). */
+int speq_group_sets_totals(const speq_group_sets* s, uint64_t* units, uint64_t* passing, uint64_t* unique,
+                           uint64_t* shared);
+void speq_group_sets_free(speq_group_sets* s);
 
 /* ---- several GPUs in one process ----
  * Reads shard across the GPUs of a node, the index is replicated (one speq_device_index per GPU, opened from the

@@ -6,6 +6,6 @@ ibharvey/speq (C++/SeqAn3); see DESIGN.md for the path, the boundary and the dat
 """
 from ._lib import SpeqError, lib  # noqa: F401  (raises if libspeq_scan.so is missing)
 from .api import (SPEQ_MODE_GLOBAL, SPEQ_MODE_LOCAL, Comm, DeviceIndex, EmHistogram, FmIndex, Groupings, Node, Pipeline,  # noqa: F401,E501
-                  ScanResult, em_refine, file_to_map, pack_records, unique_to_percent)
+                  ReadReport, ScanResult, em_refine, file_to_map, pack_records, unique_to_percent)
 
 __version__ = "0.1.0"

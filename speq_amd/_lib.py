@@ -75,6 +75,14 @@ SIGNATURES = {
     "speq_scan_reads_device_stats": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.POINTER(ScanParams), _P, _P, _U64P]),
     "speq_scan_reads": (C.c_int, [_P, C.c_char_p, C.c_char_p, _U64P, C.c_uint64, C.POINTER(ScanParams),
                                   _U64P, _F64P]),
+    "speq_report_reads_device": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.POINTER(ScanParams), _P, _P, _P]),
+    "speq_report_reads": (C.c_int, [_P, C.c_char_p, C.c_char_p, _U64P, C.c_uint64, C.POINTER(ScanParams), _P, _U64P]),
+    "speq_report_fastq": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.POINTER(ScanParams), C.c_uint32, C.POINTER(_P),
+                                    C.POINTER(StreamStats)]),
+    "speq_group_sets_count": (C.c_uint64, [_P]),
+    "speq_group_sets_get": (C.c_int, [_P, C.c_uint64, _U64P, _U64P]),
+    "speq_group_sets_totals": (C.c_int, [_P, _U64P, _U64P, _U64P, _U64P]),
+    "speq_group_sets_free": (None, [_P]),
     "speq_ref_unique": (C.c_int, [_P, C.c_uint32, _U64P, _U64P]),
     "speq_ref_unique_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P]),
     "speq_comm_unique_id": (C.c_int, [_P]),
@@ -133,7 +141,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 7  # include/speq_scan.h SPEQ_ABI_VERSION (struct layouts above)
+ABI_VERSION = 8  # include/speq_scan.h SPEQ_ABI_VERSION (struct layouts above)
 
 
 def lib() -> C.CDLL:

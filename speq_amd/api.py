@@ -23,7 +23,7 @@ import numpy as np
 from ._lib import (SPEQ_MODE_GLOBAL, SPEQ_MODE_LOCAL, BuildOpts, IndexInfo, ScanParams, Slot, SpeqError,  # noqa: F401
                    StreamStats, check, lib)
 
-__all__ = ["FmIndex", "DeviceIndex", "Node", "Pipeline", "ScanResult", "Groupings", "EmHistogram", "Comm", "file_to_map", "unique_to_percent",
+__all__ = ["FmIndex", "DeviceIndex", "Node", "Pipeline", "ScanResult", "ReadReport", "Groupings", "EmHistogram", "Comm", "file_to_map", "unique_to_percent",
            "em_refine", "pack_records", "SpeqError", "SPEQ_MODE_GLOBAL", "SPEQ_MODE_LOCAL"]
 
 
@@ -163,6 +163,24 @@ class FmIndex:
 
 
 @dataclass
+class ReadReport:
+    """Per-unit report (speq_report_reads): one row per read, or per pair."""
+    passing: np.ndarray      # passing windows (int64)
+    unique: np.ndarray       # windows unique to one group (int64)
+    shared: np.ndarray       # passing windows whose k-mer lies in >= 2 groups (int64)
+    first_group: np.ndarray  # group of the first unique window, -1 for none (int64)
+    sets: np.ndarray         # [n_units, W] uint64: bit g % 64 of word g // 64 <=> a window unique to group g
+
+    def groups(self, unit: int) -> frozenset:
+        """The group set of one unit."""
+        return _set_groups(self.sets[unit])
+
+
+def _set_groups(words) -> frozenset:
+    return frozenset(64 * w + b for w, x in enumerate(words) for b in range(64) if (int(x) >> b) & 1)
+
+
+@dataclass
 class ScanResult:
     total: int               # T: passing windows
     ambiguous: int           # reads (or pairs) whose counted windows name >= 2 groups
@@ -206,6 +224,56 @@ class DeviceIndex:
         p = ScanParams(k, phred_cutoff, int(paired), SPEQ_MODE_LOCAL if local else SPEQ_MODE_GLOBAL)
         check(lib().speq_scan_reads_device(self._h, d_seq, d_qual, d_offsets, n_reads, C.byref(p), d_counts,
                                            d_weights or None, stream or None))
+
+    def report(self, seq: bytes, qual: bytes, offsets: np.ndarray, k: int, phred_cutoff: int = 30,
+               paired: bool = False) -> ReadReport:
+        """Per-read (or per-pair) report of host reads (speq_report_reads): window counts, the first unique window's
+        group and the set of groups the unit's windows are unique to. A diagnostic pass, far slower than scan()."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(off) - 1
+        n_units = n // 2 if paired else n
+        W = (self.n_groups + 63) // 64
+        rec = np.zeros((n_units, 4), dtype=np.uint32)
+        sets = np.zeros((n_units, W), dtype=np.uint64)
+        p = ScanParams(k, phred_cutoff, int(paired), SPEQ_MODE_GLOBAL)
+        check(lib().speq_report_reads(self._h, seq, qual, _u64p(off), n, C.byref(p), rec.ctypes.data, _u64p(sets)))
+        first = rec[:, 3].astype(np.int64)
+        first[first == 0xFFFFFFFF] = -1
+        return ReadReport(rec[:, 0].astype(np.int64), rec[:, 1].astype(np.int64), rec[:, 2].astype(np.int64), first,
+                          sets)
+
+    def report_device(self, d_seq: int, d_qual: int, d_offsets: int, n_reads: int, k: int, d_reports: int,
+                      d_sets: int, phred_cutoff: int = 30, paired: bool = False, stream: int = 0) -> None:
+        """report() on HBM-resident buffers (raw device pointers, like scan_device): n_units records of four u32
+        {passing, unique, shared, first_group (0xFFFFFFFF: none)} at d_reports (16-byte aligned) and n_units * W u64
+        set words at d_sets are overwritten, asynchronously on `stream`."""
+        p = ScanParams(k, phred_cutoff, int(paired), SPEQ_MODE_GLOBAL)
+        check(lib().speq_report_reads_device(self._h, d_seq, d_qual, d_offsets, n_reads, C.byref(p), d_reports, d_sets,
+                                             stream or None))
+
+    def report_fastq(self, path1: str, path2: Optional[str] = None, k: int = 21, phred_cutoff: int = 30,
+                     threads: int = 4):
+        """The report of FASTQ(.gz) file(s) as a summary (speq_report_fastq; paired when path2 is given). Returns
+        ({frozenset(groups): units}, totals) with totals = {"units", "passing", "unique", "shared"}; the sets of two or
+        more groups are the fusion map."""
+        p = ScanParams(k, phred_cutoff, int(path2 is not None), SPEQ_MODE_GLOBAL)
+        h = C.c_void_p()
+        check(lib().speq_report_fastq(self._h, path1.encode(), path2.encode() if path2 else None, C.byref(p), threads,
+                                      C.byref(h), None))
+        try:
+            W = (self.n_groups + 63) // 64
+            words = np.zeros(W, dtype=np.uint64)
+            units = C.c_uint64()
+            out = {}
+            for i in range(lib().speq_group_sets_count(h)):
+                check(lib().speq_group_sets_get(h, i, _u64p(words), C.byref(units)))
+                out[_set_groups(words)] = units.value
+            t = [C.c_uint64() for _ in range(4)]
+            check(lib().speq_group_sets_totals(h, *[C.byref(x) for x in t]))
+            totals = dict(zip(("units", "passing", "unique", "shared"), (x.value for x in t)))
+        finally:
+            lib().speq_group_sets_free(h)
+        return out, totals
 
     AX_STATS_KEYS = ("wave_iters", "lookup_lanes", "run_lanes", "lookup_waves", "run_waves", "run_windows",
                      "deferred", "filter_pass", "p2_probes", "p2_verify", "chunks", "segments", "qual_bytes",

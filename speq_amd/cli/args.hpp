@@ -36,6 +36,7 @@ struct CmdArguments {  // include/arg_parse.h:10-28
     int gpus{1};                 // --gpus: scan on GPUs 0..N-1 of this process (0 = every visible GPU)
     std::vector<int> devices;    // --devices: explicit GPU ordinals (repeats = logical shards of one GPU)
     unsigned int max_em_iterations{1000};
+    std::filesystem::path out_file_group_sets{};  // --group-sets: the pairs' (reads') group sets, the real fusion map
 };
 
 struct ParseError : std::runtime_error {

@@ -56,6 +56,9 @@ const char* HELP =
     "      --device N            GPU ordinal (default $LOCAL_RANK or 0)\n"
     "      --gpus N              scan: shard the reads over GPUs 0..N-1 (default 1; 0 = every visible GPU)\n"
     "      --devices I,J,...     scan: shard the reads over these GPU ordinals (repeats allowed)\n"
+    "      --group-sets FILE     scan: after the scan, one more pass over the reads writes FILE: one line per distinct\n"
+    "                            set of groups that a read's (pair's) unique k-mers name, as units, number of groups,\n"
+    "                            names ('-' = none); the lines of 2 or more groups are the fusion map\n"
     "one process per GPU: run under a launcher that sets WORLD_SIZE > 1, RANK and LOCAL_RANK (e.g. torchrun\n"
     "--no-python bin/speq scan ...): each rank scans its share of the reads on GPU $LOCAL_RANK and the counts are\n"
     "summed with RCCL; rank 0 prints and writes the results ($SPEQ_RENDEZVOUS: the id file, default under /tmp)\n";
@@ -150,6 +153,7 @@ CmdArguments parse(int argc, char** argv) {
                 b = e + 1;
             }
         }
+        else if (allow_reads && opt == "--group-sets") a.out_file_group_sets = value();
         else if (allow_reads && opt == "--max-em-iterations") a.max_em_iterations = to_number<unsigned>(opt, value());
         else throw ParseError("Unknown option " + opt + ". In case this is meant to be a non-option/argument/parameter, "
                               "please specify the start of non-options with '--'.");
@@ -182,6 +186,7 @@ CmdArguments parse(int argc, char** argv) {
         a.io_file_index = idx;
     }
     check_out_file(a.out_file_path, a.is_force);
+    if (!a.out_file_group_sets.empty()) check_out_file(a.out_file_group_sets, a.is_force);
     a.is_parsed = true;
     return a;
 }
@@ -483,6 +488,34 @@ void dist_sum(const Dist& dd, void* buf, size_t n, bool f64) {
     if (dd.on() && n) ok(speq_allreduce_host(dd.comm, dd.device, buf, n, f64 ? 1 : 0), "all-reduce over ranks");
 }
 
+// FILE of --group-sets: "units<TAB>n_groups<TAB>name1,name2,..." per distinct group set, ascending by the set read as
+// one integer (the empty set, "-", first).
+void write_group_sets(const CmdArguments& a, speq_device_index* d, const speq_scan_params& prm,
+                      const std::vector<std::string>& names) {
+    speq_group_sets* gs = nullptr;
+    ok(speq_report_fastq(d, a.in_file_reads_path_1.c_str(),
+                         a.in_file_reads_path_2.empty() ? nullptr : a.in_file_reads_path_2.c_str(), &prm, a.threads, &gs,
+                         nullptr),
+       "reporting group sets");
+    std::unique_ptr<speq_group_sets, void (*)(speq_group_sets*)> guard(gs, speq_group_sets_free);
+    std::ofstream of(a.out_file_group_sets);
+    if (!of) throw CApiError("cannot write " + a.out_file_group_sets.string());
+    std::vector<uint64_t> words(SPEQ_SET_WORDS(names.size()));
+    const uint64_t n = speq_group_sets_count(gs);
+    for (uint64_t i = 0; i < n; ++i) {
+        uint64_t units = 0;
+        ok(speq_group_sets_get(gs, i, words.data(), &units), "reading group sets");
+        std::string list;
+        size_t n_groups = 0;
+        for (size_t g = 0; g < names.size(); ++g)
+            if ((words[g / 64] >> (g % 64)) & 1u) {
+                if (n_groups++) list += ",";
+                list += names[g];
+            }
+        of << units << "\t" << n_groups << "\t" << (n_groups ? list : std::string("-")) << "\n";
+    }
+}
+
 int run_scan(CmdArguments& a) {
     PhaseClock phase;
     Dist dd = dist_from_env(a);
@@ -728,6 +761,13 @@ int run_scan(CmdArguments& a) {
         std::ofstream of(a.out_file_path);
         if (!of) throw CApiError("cannot write " + a.out_file_path.string());
         for (size_t i = 0; i < G; ++i) of << h.names[i] << "\t" << percent[i] << "\n";
+    }
+    // --group-sets: one report pass over the same reads on the first replica (rank 0 of a one-process-per-GPU run),
+    // after everything the run prints and writes otherwise. The degenerate fusion-map line above stays as the
+    // reference prints it; this file is the map it meant: the lines of two or more groups.
+    if (!a.out_file_group_sets.empty()) {
+        write_group_sets(a, d, prm, h.names);
+        phase("group sets");
     }
     // The device replica, its pinned pipeline slots and the index are left to process exit: unpinning and freeing
     // them explicitly costs ~0.07 s and the process ends right after this.

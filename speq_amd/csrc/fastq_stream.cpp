@@ -27,6 +27,7 @@
 #include <cstring>
 #include <deque>
 #include <exception>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -36,6 +37,14 @@
 
 #include "capi_internal.hpp"
 #include "scan_internal.hpp"
+
+// speq_report_fastq's result: the distinct group sets in ascending order with their unit counts, and the totals
+struct speq_group_sets {
+    uint32_t W = 0;
+    std::vector<uint64_t> words;  // W per entry, least significant word first
+    std::vector<uint64_t> units;
+    uint64_t n_units = 0, passing = 0, unique = 0, shared = 0;
+};
 
 namespace {
 
@@ -780,11 +789,9 @@ struct PipelineSink final : Sink {
     }
 };
 
-// Order-independent digest of the parsed records (sum over records of a 64-bit hash of length, bases and
-// qualities), so CPU tests can check the reader/parser without a GPU.
-struct ChecksumSink final : Sink {
+// Sinks that keep parsed blocks in host memory: buffers handed out by acquire and taken back by release.
+struct HostSink : Sink {
     std::mutex mu;
-    std::atomic<uint64_t> digest{0};
     struct Held {
         std::vector<uint8_t> seq, qual;
         std::vector<uint64_t> off;
@@ -812,6 +819,16 @@ struct ChecksumSink final : Sink {
         s.cap_records = records;
         s.slot = id;
     }
+    void release(int32_t slot) {
+        std::lock_guard<std::mutex> lk(mu);
+        free_ids.push_back(slot);
+    }
+};
+
+// Order-independent digest of the parsed records (sum over records of a 64-bit hash of length, bases and
+// qualities), so CPU tests can check the reader/parser without a GPU.
+struct ChecksumSink final : HostSink {
+    std::atomic<uint64_t> digest{0};
     static uint64_t mix(uint64_t z) {
         z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
         z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
@@ -826,8 +843,48 @@ struct ChecksumSink final : Sink {
             acc += mix(h);
         }
         digest += acc;
+        release(s.slot);
+    }
+};
+
+// Per-unit report of every host-parsed block (speq_report_reads), tallied by group set: the blocks arrive in any order,
+// so the file-level result is the summary {set -> units} and the sums of the records' fields.
+struct ReportSink final : HostSink {
+    speq_device_index* d;
+    speq_scan_params params;
+    uint32_t W;
+    // keys hold the set's words most significant first, so the map's order is the order of the sets as integers
+    std::map<std::vector<uint64_t>, uint64_t> tally;
+    uint64_t units = 0, passing = 0, unique = 0, shared = 0;
+    ReportSink(speq_device_index* dev, const speq_scan_params& p)
+        : d(dev), params(p), W((uint32_t)SPEQ_SET_WORDS(speq::device_groups(dev))) {}
+    void submit(const speq_slot& s, uint64_t records) override {
+        struct Release {
+            ReportSink& sink;
+            int32_t slot;
+            ~Release() { sink.release(slot); }
+        } rel{*this, s.slot};
+        if (records == 0) return;
+        const uint64_t n_units = params.paired ? records / 2 : records;
+        std::vector<speq_read_report> rep(n_units);
+        std::vector<uint64_t> sets(n_units * W);
+        check_rc(speq_report_reads(d, s.seq, s.qual, s.offsets, records, &params, rep.data(), sets.data()));
+        std::map<std::vector<uint64_t>, uint64_t> local;
+        uint64_t p = 0, u = 0, m = 0;
+        std::vector<uint64_t> key(W);
+        for (uint64_t i = 0; i < n_units; ++i) {
+            for (uint32_t w = 0; w < W; ++w) key[w] = sets[i * W + (W - 1 - w)];
+            ++local[key];
+            p += rep[i].passing;
+            u += rep[i].unique;
+            m += rep[i].shared;
+        }
         std::lock_guard<std::mutex> lk(mu);
-        free_ids.push_back(s.slot);
+        for (const auto& e : local) tally[e.first] += e.second;
+        units += n_units;
+        passing += p;
+        unique += u;
+        shared += m;
     }
 };
 
@@ -1447,3 +1504,59 @@ extern "C" int speq_fastq_checksum(const char* path1, const char* path2, uint32_
         *digest = sink->digest.load();
     });
 }
+
+extern "C" int speq_report_fastq(speq_device_index* d, const char* path1, const char* path2,
+                                 const speq_scan_params* params, uint32_t threads, speq_group_sets** out,
+                                 speq_stream_stats* stats) {
+    return speq::guarded([&] {
+        if (!d || !path1 || !params || !out) throw std::invalid_argument("speq_report_fastq: null argument");
+        if (params->k < 1 || params->k > SPEQ_REPORT_MAX_K)
+            throw std::invalid_argument("speq_report_fastq: k must be in [1, 1024]");
+        const auto t0 = std::chrono::steady_clock::now();
+        speq_scan_params p = *params;
+        p.paired = path2 != nullptr;
+        ReportSink sink(d, p);
+        const StreamTotals tot = run_stream(path1, path2, threads, sink, false, false);
+        auto res = std::make_unique<speq_group_sets>();
+        res->W = sink.W;
+        for (const auto& e : sink.tally) {
+            for (uint32_t w = 0; w < sink.W; ++w) res->words.push_back(e.first[sink.W - 1 - w]);
+            res->units.push_back(e.second);
+        }
+        res->n_units = sink.units;
+        res->passing = sink.passing;
+        res->unique = sink.unique;
+        res->shared = sink.shared;
+        if (stats) {
+            stats->records = tot.records;
+            stats->bases = tot.bases;
+            stats->batches = tot.batches;
+            stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+        *out = res.release();
+    });
+}
+
+extern "C" uint64_t speq_group_sets_count(const speq_group_sets* s) { return s ? s->units.size() : 0; }
+
+extern "C" int speq_group_sets_get(const speq_group_sets* s, uint64_t i, uint64_t* words, uint64_t* units) {
+    return speq::guarded([&] {
+        if (!s || !words || !units) throw std::invalid_argument("speq_group_sets_get: null argument");
+        if (i >= s->units.size()) throw std::invalid_argument("speq_group_sets_get: index out of range");
+        std::copy(s->words.begin() + i * s->W, s->words.begin() + (i + 1) * s->W, words);
+        *units = s->units[i];
+    });
+}
+
+extern "C" int speq_group_sets_totals(const speq_group_sets* s, uint64_t* units, uint64_t* passing, uint64_t* unique,
+                                      uint64_t* shared) {
+    return speq::guarded([&] {
+        if (!s) throw std::invalid_argument("speq_group_sets_totals: null argument");
+        if (units) *units = s->n_units;
+        if (passing) *passing = s->passing;
+        if (unique) *unique = s->unique;
+        if (shared) *shared = s->shared;
+    });
+}
+
+extern "C" void speq_group_sets_free(speq_group_sets* s) { delete s; }
