@@ -161,7 +161,8 @@ int speq_scan_reads_device(speq_device_index* d, const uint8_t* d_seq, const uin
  * blocks 0-255, 256-511, 512-767, 768-1023 and 1024 on, [37] probes of the substitution bitmap (tuning "ax_sproof"),
  * [38] windows over a mismatch dropped on its proof (not looked up, not deferred), [39] proofs whose continued run met
  * a second mismatch within k - 1 bases (the windows over both deferred). Fails with SPEQ_E_ARG when the scan does not
- * use that kernel. */
+ * use that kernel, and, before anything is launched (counts, weights and stats untouched), when the replica has more
+ * than 2048 groups: the instrumented kernel exists with the LDS tally only. */
 #define SPEQ_AX_STATS_N 40
 int speq_scan_reads_device_stats(speq_device_index* d, const uint8_t* d_seq, const uint8_t* d_qual,
                                  const uint64_t* d_offsets, uint64_t n_reads, const speq_scan_params* params,
@@ -422,7 +423,15 @@ void speq_groupings_free(speq_groupings* g);
  *                  same), "ax_sproof" substitution-bitmap proofs of the windows over a known mismatch (1: on, 0: off,
  *                  2 default: on for the k whose structures have no m-mer filter; the bitmap of a k is built by
  *                  speq_device_prepare or the first scan that uses it; results are the same);
- *                  "last_kernel" (read only) the kernel of the last scan. */
+ *                  "last_kernel" (read only) the kernel of the last scan: 0 LF steps (k_scan), 1 k-mer table (k_scan),
+ *                  2 pipelined k-mer table (k_scan_kt), 3 anchor-and-extend (k_scan_ax);
+ *                  "last_variant" (read only) the template instantiation of the last launch of one of these kernels,
+ *                  the reference-uniqueness pass included (-1 before the first): bits 0-1 family (0 k_scan,
+ *                  1 k_scan_kt, 2 k_scan_ax), bits 2-3 mode (0 global, 1 local, 2 reference pass), bit 4 paired,
+ *                  bit 5 the tally in LDS (G <= 2048; else global atomics), bit 6 EM histogram, bits 7-9 windows per
+ *                  lane (k_scan 1, 2, 4; k_scan_kt 1, 2) or 64-bit words per k-mer (k_scan_ax 1..4), bit 10 k_scan
+ *                  with a k-mer table, bit 11 compact table, bit 12 substitution-bitmap path, bit 13 the instrumented
+ *                  twin. A test ledger (tests/variant_table.py) states which value every scan must report. */
 int speq_device_set_tuning(speq_device_index* d, const char* key, int64_t value);
 int speq_device_get_tuning(const speq_device_index* d, const char* key, int64_t* value);
 

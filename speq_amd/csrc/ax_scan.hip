@@ -1739,9 +1739,11 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
     }
 }
 
+// (ax_launch_one, _nwc and _mode return the instantiation launched, packed from ax_launch_one's own template
+// arguments: tuning key "last_variant")
 template <int MODE, bool PAIRED, bool LDS, bool EM, int HW, bool STATS, bool SP = false>
-void ax_launch_one(const AxView& A, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st,
-                   unsigned long long* a, double* w, uint32_t n_cus) {
+int ax_launch_one(const AxView& A, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st,
+                  unsigned long long* a, double* w, uint32_t n_cus) {
     if (lds > 64 * 1024)  // dynamic LDS above 64 KiB must be allowed (occupancy caps pad it)
         HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan_ax<MODE, PAIRED, LDS, EM, HW, STATS, SP>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1765,35 +1767,35 @@ void ax_launch_one(const AxView& A, const UnitSrc& src, uint32_t grid, size_t ld
     grid = std::min<uint32_t>(grid, (uint32_t)per_cu * n_cus);
     hipLaunchKernelGGL((k_scan_ax<MODE, PAIRED, LDS, EM, HW, STATS, SP>), dim3(grid), dim3(AX_THREADS), lds, st, A, src,
                        a, w);
+    return speq::scan_variant(speq::VARIANT_K_SCAN_AX, MODE, PAIRED, LDS, EM, HW, false, false, SP, STATS);
 }
 
 // HW by k: 1 (k <= 32), 2 (k <= 64), 3 (k <= 96: the reference's default k = 70), 4 (k <= 128)
 template <int MODE, bool PAIRED, bool LDS, bool EM, bool STATS>
-void ax_launch_nwc(uint32_t k, const AxView& A, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st,
-                   unsigned long long* a, double* w, uint32_t n_cus) {
+int ax_launch_nwc(uint32_t k, const AxView& A, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st,
+                  unsigned long long* a, double* w, uint32_t n_cus) {
     if (k <= 32 && SPEQ_AX_SPROOF && A.s_bytes != 0u)
-        ax_launch_one<MODE, PAIRED, LDS, EM, 1, STATS, SPEQ_AX_SPROOF != 0>(A, src, grid, lds, st, a, w, n_cus);
-    else if (k <= 32) ax_launch_one<MODE, PAIRED, LDS, EM, 1, STATS>(A, src, grid, lds, st, a, w, n_cus);
-    else if (k <= 64) ax_launch_one<MODE, PAIRED, LDS, EM, 2, STATS>(A, src, grid, lds, st, a, w, n_cus);
-    else if (k <= 96) ax_launch_one<MODE, PAIRED, LDS, EM, 3, STATS>(A, src, grid, lds, st, a, w, n_cus);
-    else ax_launch_one<MODE, PAIRED, LDS, EM, 4, STATS>(A, src, grid, lds, st, a, w, n_cus);
+        return ax_launch_one<MODE, PAIRED, LDS, EM, 1, STATS, SPEQ_AX_SPROOF != 0>(A, src, grid, lds, st, a, w, n_cus);
+    if (k <= 32) return ax_launch_one<MODE, PAIRED, LDS, EM, 1, STATS>(A, src, grid, lds, st, a, w, n_cus);
+    if (k <= 64) return ax_launch_one<MODE, PAIRED, LDS, EM, 2, STATS>(A, src, grid, lds, st, a, w, n_cus);
+    if (k <= 96) return ax_launch_one<MODE, PAIRED, LDS, EM, 3, STATS>(A, src, grid, lds, st, a, w, n_cus);
+    return ax_launch_one<MODE, PAIRED, LDS, EM, 4, STATS>(A, src, grid, lds, st, a, w, n_cus);
 }
 
+// (the instrumented twin exists with the LDS tally and without an EM histogram only; speq_scan_reads_device_stats
+// refuses a replica of more than LDS_HIST_MAX_G groups before it gets here, and passes no histogram)
 template <int MODE, bool PAIRED>
-void ax_launch_mode(bool lds_hist, uint32_t k, const AxView& A, const UnitSrc& src, uint32_t grid, size_t lds,
-                    hipStream_t st, unsigned long long* a, double* w, uint32_t n_cus) {
+int ax_launch_mode(bool lds_hist, uint32_t k, const AxView& A, const UnitSrc& src, uint32_t grid, size_t lds,
+                   hipStream_t st, unsigned long long* a, double* w, uint32_t n_cus) {
     const bool em = src.em_mult != nullptr;
-    if (A.stats != nullptr && lds_hist && !em) {
-        ax_launch_nwc<MODE, PAIRED, true, false, true>(k, A, src, grid, lds, st, a, w, n_cus);
-        return;
-    }
+    if (A.stats != nullptr && lds_hist && !em)
+        return ax_launch_nwc<MODE, PAIRED, true, false, true>(k, A, src, grid, lds, st, a, w, n_cus);
     if (lds_hist) {
-        if (em) ax_launch_nwc<MODE, PAIRED, true, true, false>(k, A, src, grid, lds, st, a, w, n_cus);
-        else ax_launch_nwc<MODE, PAIRED, true, false, false>(k, A, src, grid, lds, st, a, w, n_cus);
-    } else {
-        if (em) ax_launch_nwc<MODE, PAIRED, false, true, false>(k, A, src, grid, lds, st, a, w, n_cus);
-        else ax_launch_nwc<MODE, PAIRED, false, false, false>(k, A, src, grid, lds, st, a, w, n_cus);
+        if (em) return ax_launch_nwc<MODE, PAIRED, true, true, false>(k, A, src, grid, lds, st, a, w, n_cus);
+        return ax_launch_nwc<MODE, PAIRED, true, false, false>(k, A, src, grid, lds, st, a, w, n_cus);
     }
+    if (em) return ax_launch_nwc<MODE, PAIRED, false, true, false>(k, A, src, grid, lds, st, a, w, n_cus);
+    return ax_launch_nwc<MODE, PAIRED, false, false, false>(k, A, src, grid, lds, st, a, w, n_cus);
 }
 
 }  // namespace
@@ -2075,13 +2077,15 @@ bool launch_ax(speq_device_index* d, int mode, bool paired, const UnitSrc& src, 
     }
     const uint32_t grid = (uint32_t)blocks;
     const uint32_t slots = d->n_cus * d->ax_generations;  // (the grid cap: resident blocks per CU x slots)
+    int lv;
     if (mode == KM_GLOBAL) {
-        if (paired) ax_launch_mode<KM_GLOBAL, true>(lds_hist, src.k, A, src, grid, lds_launch, st, a, w, slots);
-        else ax_launch_mode<KM_GLOBAL, false>(lds_hist, src.k, A, src, grid, lds_launch, st, a, w, slots);
+        if (paired) lv = ax_launch_mode<KM_GLOBAL, true>(lds_hist, src.k, A, src, grid, lds_launch, st, a, w, slots);
+        else lv = ax_launch_mode<KM_GLOBAL, false>(lds_hist, src.k, A, src, grid, lds_launch, st, a, w, slots);
     } else {
-        if (paired) ax_launch_mode<KM_LOCAL, true>(lds_hist, src.k, A, src, grid, lds_launch, st, a, w, slots);
-        else ax_launch_mode<KM_LOCAL, false>(lds_hist, src.k, A, src, grid, lds_launch, st, a, w, slots);
+        if (paired) lv = ax_launch_mode<KM_LOCAL, true>(lds_hist, src.k, A, src, grid, lds_launch, st, a, w, slots);
+        else lv = ax_launch_mode<KM_LOCAL, false>(lds_hist, src.k, A, src, grid, lds_launch, st, a, w, slots);
     }
+    d->last_variant = lv;
     HIP_OK(hipGetLastError());
     return true;
 }

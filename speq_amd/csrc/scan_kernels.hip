@@ -1445,18 +1445,30 @@ const speq_device_index::KmerTable* ensure_ktab(speq_device_index* d, uint32_t k
     return it->second.table ? &it->second : nullptr;  // null table: too large, LF steps
 }
 
+// One launch of k_scan_kt / k_scan; each returns the instantiation it launched (tuning key "last_variant"), packed
+// from the template arguments of the launch itself.
+template <int MODE, bool PAIRED, bool LDS, bool EM, int NW, bool CK>
+int launch_kt_one(const DevView& v, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st,
+                  unsigned long long* a, double* w) {
+    hipLaunchKernelGGL((k_scan_kt<MODE, PAIRED, LDS, EM, NW, CK>), dim3(grid), dim3(BLOCK_THREADS), lds, st, v, src, a,
+                       w);
+    return speq::scan_variant(speq::VARIANT_K_SCAN_KT, MODE, PAIRED, LDS, EM, NW, false, CK);
+}
+
+template <int MODE, bool PAIRED, bool LDS, int NWIN, bool EM, bool KT>
+int launch_v_one(const DevView& v, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st,
+                 unsigned long long* a, unsigned long long* b, double* w) {
+    hipLaunchKernelGGL((k_scan<MODE, PAIRED, LDS, NWIN, EM, KT>), dim3(grid), dim3(BLOCK_THREADS), lds, st, v, src, a,
+                       b, w);
+    return speq::scan_variant(speq::VARIANT_K_SCAN, MODE, PAIRED, LDS, EM, NWIN, KT);
+}
+
 template <int MODE, bool PAIRED, bool LDS, bool CK>
-void launch_kt(const DevView& v, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st, unsigned long long* a,
-               double* w, uint32_t ilp) {
-    if (src.em_mult != nullptr)
-        hipLaunchKernelGGL((k_scan_kt<MODE, PAIRED, LDS, true, 1, CK>), dim3(grid), dim3(BLOCK_THREADS), lds, st, v,
-                           src, a, w);
-    else if (ilp == 2)
-        hipLaunchKernelGGL((k_scan_kt<MODE, PAIRED, LDS, false, 2, CK>), dim3(grid), dim3(BLOCK_THREADS), lds, st, v,
-                           src, a, w);
-    else
-        hipLaunchKernelGGL((k_scan_kt<MODE, PAIRED, LDS, false, 1, CK>), dim3(grid), dim3(BLOCK_THREADS), lds, st, v,
-                           src, a, w);
+int launch_kt(const DevView& v, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st, unsigned long long* a,
+              double* w, uint32_t ilp) {
+    if (src.em_mult != nullptr) return launch_kt_one<MODE, PAIRED, LDS, true, 1, CK>(v, src, grid, lds, st, a, w);
+    if (ilp == 2) return launch_kt_one<MODE, PAIRED, LDS, false, 2, CK>(v, src, grid, lds, st, a, w);
+    return launch_kt_one<MODE, PAIRED, LDS, false, 1, CK>(v, src, grid, lds, st, a, w);
 }
 
 template <int MODE, bool PAIRED, bool LDS, bool KT>
@@ -1464,25 +1476,22 @@ void launch_v(const speq_device_index* d, const DevView& v, const UnitSrc& src, 
               hipStream_t st, unsigned long long* a, unsigned long long* b, double* w) {
     const uint32_t ilp = KT ? (d->ilp_kt ? d->ilp_kt : (v.kt_compact ? 1u : 2u))
                             : (MODE == KM_LOCAL ? d->ilp_local : d->ilp);
+    int& variant = const_cast<speq_device_index*>(d)->last_variant;
     if constexpr (KT && MODE != KM_REF) {
         if (ilp <= 2 && d->kt_pipeline) {  // software-pipelined table scan
-            if (v.kt_compact) launch_kt<MODE, PAIRED, LDS, true>(v, src, grid, lds, st, a, w, ilp);
-            else launch_kt<MODE, PAIRED, LDS, false>(v, src, grid, lds, st, a, w, ilp);
+            if (v.kt_compact) variant = launch_kt<MODE, PAIRED, LDS, true>(v, src, grid, lds, st, a, w, ilp);
+            else variant = launch_kt<MODE, PAIRED, LDS, false>(v, src, grid, lds, st, a, w, ilp);
             return;
         }
     }
     if (MODE != KM_REF && src.em_mult != nullptr)
-        hipLaunchKernelGGL((k_scan<MODE, PAIRED, LDS, 1, MODE != KM_REF, KT>), dim3(grid), dim3(BLOCK_THREADS), lds,
-                           st, v, src, a, b, w);
+        variant = launch_v_one<MODE, PAIRED, LDS, 1, MODE != KM_REF, KT>(v, src, grid, lds, st, a, b, w);
     else if (KT && MODE == KM_GLOBAL && ilp == 4)
-        hipLaunchKernelGGL((k_scan<MODE, PAIRED, LDS, 4, false, KT>), dim3(grid), dim3(BLOCK_THREADS), lds, st, v,
-                           src, a, b, w);
+        variant = launch_v_one<MODE, PAIRED, LDS, 4, false, KT>(v, src, grid, lds, st, a, b, w);
     else if (ilp >= 2)
-        hipLaunchKernelGGL((k_scan<MODE, PAIRED, LDS, 2, false, KT>), dim3(grid), dim3(BLOCK_THREADS), lds, st, v,
-                           src, a, b, w);
+        variant = launch_v_one<MODE, PAIRED, LDS, 2, false, KT>(v, src, grid, lds, st, a, b, w);
     else
-        hipLaunchKernelGGL((k_scan<MODE, PAIRED, LDS, 1, false, KT>), dim3(grid), dim3(BLOCK_THREADS), lds, st, v,
-                           src, a, b, w);
+        variant = launch_v_one<MODE, PAIRED, LDS, 1, false, KT>(v, src, grid, lds, st, a, b, w);
 }
 
 template <int MODE, bool PAIRED, bool LDS>
@@ -1803,6 +1812,12 @@ int speq_scan_reads_device_stats(speq_device_index* d, const uint8_t* d_seq, con
                                  uint64_t* d_counts, double* d_weights, uint64_t* stats) {
     return speq::guarded([&] {
         if (!d || !stats) throw std::invalid_argument("speq_scan_reads_device_stats: null argument");
+        // the instrumented instantiations tally in LDS only: with more groups the plain kernel would run and leave
+        // every counter zero, so refuse before anything is allocated or launched
+        if (d->G > LDS_HIST_MAX_G)
+            throw std::invalid_argument("speq_scan_reads_device_stats: the instrumented kernel takes at most " +
+                                        std::to_string(LDS_HIST_MAX_G) + " groups (this replica has " +
+                                        std::to_string(d->G) + ")");
         DeviceGuard g(d->device);
         // the counters' buffer travels with this launch only (UnitSrc::ax_stats), so ordinary scans of the same
         // replica from other threads never run the instrumented kernel
@@ -2268,6 +2283,7 @@ int speq_device_get_tuning(const speq_device_index* d, const char* key, int64_t*
         else if (k == "kt_load8") *value = d->kt_load8;
         else if (k == "ax_scan") *value = d->ax_scan ? 1 : 0;
         else if (k == "last_kernel") *value = d->last_kernel;
+        else if (k == "last_variant") *value = d->last_variant;
         else if (k == "ax_mproof") *value = d->ax_mproof;
         else if (k == "ax_sproof") *value = d->ax_sproof;
         else if (k == "ax_load") *value = speq::ax_effective_load(d);

@@ -134,7 +134,9 @@ def test_empty_and_short_inputs(edge):
 
 
 def test_many_groups_global_atomics():
-    """G > 2048 takes the global-atomic tally path of the kernel."""
+    """G > 2048 takes the global-atomic tally (LDS_HIST = false), here at G = 2500, k = 25, single-end, no EM
+    histogram. Every other instantiation of that plane (paired, EM, HW 2..4, both table forms, the table-reading
+    k_scan) is reached and checked by tests/test_gpu_variants.py."""
     G = 2500
     ref = synth.make_reference(G, 1, 300)
     reads = synth.make_reads(ref, 4_000, read_len=100)
