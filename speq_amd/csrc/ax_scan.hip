@@ -375,8 +375,8 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t G = A.G, k = src.k;
-    const uint32_t hist_words = LDS_HIST ? ((MODE == KM_GLOBAL) ? G : 2u * G) : 0u;
-    const uint32_t hist_bytes = (hist_words * 8u + 15u) & ~15u;
+    const uint32_t hist_words = hist_region_words(MODE, G, LDS_HIST, false);  // (T and ambiguous: per wave, below)
+    const uint32_t hist_bytes = hist_region_bytes(MODE, G, LDS_HIST, false);
     unsigned long long* hA = reinterpret_cast<unsigned long long*>(smem);
     double* hW = reinterpret_cast<double*>(hA + G);
     // KM_LOCAL: ftab[min(byte, 75)] = fl(1 / lut[q]) of the quality byte's rank q (bytes <= 33 rank 0, >= 74 rank 41;
@@ -1739,10 +1739,8 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
     }
 }
 
-// (ax_launch_one, _nwc and _mode return the instantiation launched, packed from ax_launch_one's own template
-// arguments: tuning key "last_variant")
-template <int MODE, bool PAIRED, bool LDS, bool EM, int HW, bool STATS, bool SP = false>
-int ax_launch_one(const AxView& A, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st,
+template <int MODE, bool PAIRED, bool LDS, bool EM, int HW, bool STATS, bool SP>
+void ax_launch_one(const AxView& A, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st,
                   unsigned long long* a, double* w, uint32_t n_cus) {
     if (lds > 64 * 1024)  // dynamic LDS above 64 KiB must be allowed (occupancy caps pad it)
         HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan_ax<MODE, PAIRED, LDS, EM, HW, STATS, SP>),
@@ -1767,35 +1765,6 @@ int ax_launch_one(const AxView& A, const UnitSrc& src, uint32_t grid, size_t lds
     grid = std::min<uint32_t>(grid, (uint32_t)per_cu * n_cus);
     hipLaunchKernelGGL((k_scan_ax<MODE, PAIRED, LDS, EM, HW, STATS, SP>), dim3(grid), dim3(AX_THREADS), lds, st, A, src,
                        a, w);
-    return speq::scan_variant(speq::VARIANT_K_SCAN_AX, MODE, PAIRED, LDS, EM, HW, false, false, SP, STATS);
-}
-
-// HW by k: 1 (k <= 32), 2 (k <= 64), 3 (k <= 96: the reference's default k = 70), 4 (k <= 128)
-template <int MODE, bool PAIRED, bool LDS, bool EM, bool STATS>
-int ax_launch_nwc(uint32_t k, const AxView& A, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st,
-                  unsigned long long* a, double* w, uint32_t n_cus) {
-    if (k <= 32 && SPEQ_AX_SPROOF && A.s_bytes != 0u)
-        return ax_launch_one<MODE, PAIRED, LDS, EM, 1, STATS, SPEQ_AX_SPROOF != 0>(A, src, grid, lds, st, a, w, n_cus);
-    if (k <= 32) return ax_launch_one<MODE, PAIRED, LDS, EM, 1, STATS>(A, src, grid, lds, st, a, w, n_cus);
-    if (k <= 64) return ax_launch_one<MODE, PAIRED, LDS, EM, 2, STATS>(A, src, grid, lds, st, a, w, n_cus);
-    if (k <= 96) return ax_launch_one<MODE, PAIRED, LDS, EM, 3, STATS>(A, src, grid, lds, st, a, w, n_cus);
-    return ax_launch_one<MODE, PAIRED, LDS, EM, 4, STATS>(A, src, grid, lds, st, a, w, n_cus);
-}
-
-// (the instrumented twin exists with the LDS tally and without an EM histogram only; speq_scan_reads_device_stats
-// refuses a replica of more than LDS_HIST_MAX_G groups before it gets here, and passes no histogram)
-template <int MODE, bool PAIRED>
-int ax_launch_mode(bool lds_hist, uint32_t k, const AxView& A, const UnitSrc& src, uint32_t grid, size_t lds,
-                   hipStream_t st, unsigned long long* a, double* w, uint32_t n_cus) {
-    const bool em = src.em_mult != nullptr;
-    if (A.stats != nullptr && lds_hist && !em)
-        return ax_launch_nwc<MODE, PAIRED, true, false, true>(k, A, src, grid, lds, st, a, w, n_cus);
-    if (lds_hist) {
-        if (em) return ax_launch_nwc<MODE, PAIRED, true, true, false>(k, A, src, grid, lds, st, a, w, n_cus);
-        return ax_launch_nwc<MODE, PAIRED, true, false, false>(k, A, src, grid, lds, st, a, w, n_cus);
-    }
-    if (em) return ax_launch_nwc<MODE, PAIRED, false, true, false>(k, A, src, grid, lds, st, a, w, n_cus);
-    return ax_launch_nwc<MODE, PAIRED, false, false, false>(k, A, src, grid, lds, st, a, w, n_cus);
 }
 
 }  // namespace
@@ -1999,7 +1968,7 @@ static bool ensure_ax_em(speq_device_index* d, AxTable* ax, uint32_t k) {
     d->track(mlo);
     d->track(mhi);
     ax->mhi = mhi;
-    ax->mlo = mlo;  // last: the unlocked check in launch_ax reads it
+    ax->mlo = mlo;  // last: the unlocked check in ax_facts reads it
     ax->bytes += (n + 64) * 8;
     return true;
 }
@@ -2030,64 +1999,52 @@ bool ensure_ax_sproof(speq_device_index* d, AxTable* ax, uint32_t k) {
     HIP_OK(hipStreamSynchronize(d->stream));
     ax->s_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     ax->build_ms += ax->s_build_ms;
-    ax->s_ready = true;  // last: the unlocked check in launch_ax reads it
+    ax->s_ready = true;  // last: the unlocked check in ax_facts reads it
     return true;
 }
 
-// Launches k_scan_ax for a read scan (mode 0 global, 1 local) when replica d has (or can build) the structures of
-// src.k; returns false when the caller must use another kernel. With src.ax_stats set (speq_scan_reads_device_stats:
-// a per-call buffer, so concurrent ordinary scans of the replica never see it), the diagnostic instantiation also adds
-// its work counters there.
-bool launch_ax(speq_device_index* d, int mode, bool paired, const UnitSrc& src, hipStream_t st, unsigned long long* a,
-               double* w) {
-    if (src.n_units >= (1ull << 32)) return false;  // 32-bit read indices in the kernel: the other kernels take it
+// The anchor kernel's share of the facts of a read scan (scan_plan.hpp), gathered lazily: the structures of src.k
+// first, their EM arrays for an EM scan only, the substitution bitmap on its first use.
+const AxTable* ax_facts(speq_device_index* d, const UnitSrc& src, ScanFacts& f) {
+    f.ax_wpb = AX_WPB;
+    f.ax_wave_bytes = f.mode == KM_LOCAL ? ax_wave_bytes<KM_LOCAL>() : ax_wave_bytes<KM_GLOBAL>();
+    if (src.n_units >= AX_MAX_UNITS) return nullptr;  // (before anything is built for a scan the kernel refuses)
     AxTable* ax = const_cast<AxTable*>(ensure_ax(d, src.k));
-    if (!ax) return false;
-    if (src.em_mult != nullptr && !ensure_ax_em(d, ax, src.k)) return false;  // EM: the other kernels take it
+    if (!ax) return nullptr;
+    if (src.em_mult != nullptr && !ensure_ax_em(d, ax, src.k)) return nullptr;  // EM: the other kernels take it
+    f.ax_usable = true;
+    f.sproof_active = ax_sproof_on(d, *ax, src.k) && (ax->s_ready || ensure_ax_sproof(d, ax, src.k));
+    return ax;
+}
+
+// Launches the k_scan_ax instantiation of plan p. With src.ax_stats set (speq_scan_reads_device_stats: a per-call
+// buffer, so concurrent ordinary scans of the replica never see it), the diagnostic instantiation also adds its work
+// counters there.
+void launch_ax(const speq_device_index* d, const AxTable& ax, const ScanPlan& p, const UnitSrc& src, hipStream_t st,
+               unsigned long long* a, double* w) {
     AxView A;
-    A.gran = reinterpret_cast<const u32x4*>(ax->gran);
-    A.mlo = ax->mlo;
-    A.mhi = ax->mhi;
-    A.atab = reinterpret_cast<const unsigned long long*>(ax->atab);
-    A.filt = reinterpret_cast<const unsigned long long*>(ax->filt);
+    A.gran = reinterpret_cast<const u32x4*>(ax.gran);
+    A.mlo = ax.mlo;
+    A.mhi = ax.mhi;
+    A.atab = reinterpret_cast<const unsigned long long*>(ax.atab);
+    A.filt = reinterpret_cast<const unsigned long long*>(ax.filt);
     A.stats = src.ax_stats;
-    A.nb = ax->nb;
-    A.nf = ax->nf;
+    A.nb = ax.nb;
+    A.nf = ax.nf;
     A.n = d->view.n;
-    A.gran_bytes = ax->gran_bytes;
-    A.m = d->ax_mproof ? ax->m : 0u;
+    A.gran_bytes = ax.gran_bytes;
+    A.m = d->ax_mproof ? ax.m : 0u;
     A.mtiles = d->ax_mproof == 1u ? 1u : 0u;
-    A.nmf = A.m ? ax->nmf : 0u;
-    A.mf_off = (uint32_t)(ax->nb * 64u);
-    const bool sproof = ax_sproof_on(d, *ax, src.k) && (ax->s_ready || ensure_ax_sproof(d, ax, src.k));
-    A.s_off = (uint32_t)ax->s_off;
-    A.s_bytes = sproof ? (uint32_t)(ax->s_words * 8u + 16u) : 0u;
+    A.nmf = A.m ? ax.nmf : 0u;
+    A.mf_off = (uint32_t)(ax.nb * 64u);
+    A.s_off = (uint32_t)ax.s_off;
+    A.s_bytes = p.variant.sproof ? (uint32_t)(ax.s_words * 8u + 16u) : 0u;
     A.G = d->G;
-    const bool lds_hist = d->G <= LDS_HIST_MAX_G;
-    const uint32_t hist_words = lds_hist ? (mode == KM_GLOBAL ? d->G : 2u * d->G) : 0u;
-    const size_t lds = ((hist_words * 8u + 15u) & ~15u) + (mode == KM_LOCAL ? QTAB_BYTES : 0u) +
-                       (size_t)AX_WPB * (mode == KM_LOCAL ? ax_wave_bytes<KM_LOCAL>() : ax_wave_bytes<KM_GLOBAL>());
-    const uint64_t reads = src.n_units;
-    uint64_t blocks = (reads + 64 * AX_WPB - 1) / (64 * AX_WPB);
-    blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, d->grid_blocks_ax));
-    size_t lds_launch = lds;
-    if (d->blocks_per_cu_ax > 0) {
-        const size_t pad = (160u * 1024u) / d->blocks_per_cu_ax;
-        if (pad > lds_launch) lds_launch = pad & ~(size_t)15;
-    }
-    const uint32_t grid = (uint32_t)blocks;
-    const uint32_t slots = d->n_cus * d->ax_generations;  // (the grid cap: resident blocks per CU x slots)
-    int lv;
-    if (mode == KM_GLOBAL) {
-        if (paired) lv = ax_launch_mode<KM_GLOBAL, true>(lds_hist, src.k, A, src, grid, lds_launch, st, a, w, slots);
-        else lv = ax_launch_mode<KM_GLOBAL, false>(lds_hist, src.k, A, src, grid, lds_launch, st, a, w, slots);
-    } else {
-        if (paired) lv = ax_launch_mode<KM_LOCAL, true>(lds_hist, src.k, A, src, grid, lds_launch, st, a, w, slots);
-        else lv = ax_launch_mode<KM_LOCAL, false>(lds_hist, src.k, A, src, grid, lds_launch, st, a, w, slots);
-    }
-    d->last_variant = lv;
-    HIP_OK(hipGetLastError());
-    return true;
+    with_variant<VARIANT_K_SCAN_AX>(p.variant, [&](auto packed) {
+        constexpr ScanVariant V = ScanVariant::unpack(decltype(packed)::value);
+        ax_launch_one<V.mode, V.paired, V.lds_hist, V.em, V.width, V.stats, V.sproof>(A, src, p.grid, p.lds_launch, st,
+                                                                                       a, w, p.grid_slots);
+    });
 }
 
 }  // namespace speq

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <map>
 #include <mutex>
@@ -121,33 +122,13 @@ struct speq_device_index {
     double timed_ms = 0.0;
     uint64_t timed_launches = 0;
     // kernel of the last read scan (tuning key "last_kernel", read only): 0 LF steps (k_scan), 1 k-mer table
-    // (k_scan, KT), 2 pipelined k-mer table (k_scan_kt), 3 anchor-and-extend (k_scan_ax)
-    int last_kernel = -1;
-    // template instantiation of the last launch of a scan kernel, the reference-uniqueness pass included (tuning key
-    // "last_variant", read only; speq::scan_variant below; -1 before the first launch). One host-side store per launch.
-    int last_variant = -1;
+    // (k_scan, KT), 2 pipelined k-mer table (k_scan_kt), 3 anchor-and-extend (k_scan_ax); and the template
+    // instantiation of the last launch of a scan kernel, the reference-uniqueness pass included (tuning key
+    // "last_variant", read only: speq::ScanVariant::pack, scan_plan.hpp). -1 before the first launch. Launches come
+    // from several host threads: each stores both once, relaxed, from its plan.
+    std::atomic<int> last_kernel{-1};
+    std::atomic<int> last_variant{-1};
 };
-
-namespace speq {
-// The packed value of tuning key "last_variant": which instantiation of k_scan, k_scan_kt or k_scan_ax a launch took.
-//   bits 0-1   family   0 k_scan<MODE, PAIRED, LDS_HIST, NWIN, EM, KT>, 1 k_scan_kt<MODE, PAIRED, LDS_HIST, EM, NW, CK>,
-//                       2 k_scan_ax<MODE, PAIRED, LDS_HIST, EM, HW, STATS, SP>
-//   bits 2-3   mode     0 global, 1 local, 2 the reference-uniqueness pass (KM_GLOBAL, KM_LOCAL, KM_REF)
-//   bit  4     paired
-//   bit  5     lds_hist (G <= LDS_HIST_MAX_G: the tally in LDS; else global atomics)
-//   bit  6     em       (the EM-histogram instantiation)
-//   bits 7-9   width    NWIN (1, 2, 4), NW (1, 2) or HW (1..4)
-//   bit  10    kt       k_scan reads a k-mer table (always 0 for the other families)
-//   bit  11    compact  k_scan_kt reads the compact 8-B-slot table (CK)
-//   bit  12    sproof   k_scan_ax with the substitution-bitmap path (SP)
-//   bit  13    stats    k_scan_ax's instrumented twin (STATS)
-enum { VARIANT_K_SCAN = 0, VARIANT_K_SCAN_KT = 1, VARIANT_K_SCAN_AX = 2 };
-constexpr int scan_variant(int family, int mode, bool paired, bool lds_hist, bool em, int width, bool kt = false,
-                           bool compact = false, bool sproof = false, bool stats = false) {
-    return family | mode << 2 | (int)paired << 4 | (int)lds_hist << 5 | (int)em << 6 | width << 7 | (int)kt << 10 |
-           (int)compact << 11 | (int)sproof << 12 | (int)stats << 13;
-}
-}  // namespace speq
 
 namespace speq {
 DevView search_view(const speq_device_index* d, uint32_t k);  // the FM view a search of k-mers uses (scan_kernels.hip)
@@ -156,6 +137,10 @@ const AxTable* ensure_ax(speq_device_index* d, uint32_t k);
 uint32_t ax_effective_load(const speq_device_index* d);  // the anchor table's load factor (percent) builds use
 bool ax_sproof_on(const speq_device_index* d, const AxTable& ax, uint32_t k);  // tuning "ax_sproof" applied to k
 bool ensure_ax_sproof(speq_device_index* d, AxTable* ax, uint32_t k);  // fills the substitution bitmap (once per k)
-bool launch_ax(speq_device_index* d, int mode, bool paired, const speq_dev::UnitSrc& src, hipStream_t st,
-               unsigned long long* a, double* w);
+// The anchor kernel's part of a read scan's facts (ax_usable, sproof_active, its workgroup's LDS), building what the
+// scan of src.k needs and has not got; the table, or null when another kernel must take the scan. launch_ax: the
+// launch of plan p (family k_scan_ax) with that table.
+const AxTable* ax_facts(speq_device_index* d, const speq_dev::UnitSrc& src, ScanFacts& f);
+void launch_ax(const speq_device_index* d, const AxTable& ax, const ScanPlan& p, const speq_dev::UnitSrc& src,
+               hipStream_t st, unsigned long long* a, double* w);
 }  // namespace speq

@@ -8,19 +8,14 @@
 #include <string>
 #include <vector>
 
+#include "scan_plan.hpp"
 #include "speq_errors.hpp"
 
 namespace speq_dev {
 
 
-constexpr uint32_t WAVES_PER_BLOCK = 4;
-constexpr uint32_t BLOCK_THREADS = 64 * WAVES_PER_BLOCK;
+// (the block shape, KM_*, and the LDS layout the host plans and the kernels carve up: scan_plan.hpp)
 constexpr uint32_t MAX_K = 4096;
-constexpr uint32_t LDS_HIST_MAX_G = 2048;
-constexpr uint32_t QLUT_LEN = 42;  // phred42 ranks 0..41
-// local mode, per block in LDS: {1 - 10^(-q/10), its reciprocal} for q = 0..41, then (k_scan_kt) the weight of a window
-// of k bases that all have quality q
-constexpr uint32_t QTAB_BYTES = QLUT_LEN * 24u;
 
 // a / b correctly rounded (IEEE division) from y = RN(1 / b) by two FMA corrections: q0 = a y is within 2 ulp, the
 // first correction makes it faithful, and from a faithful quotient the second gives the correctly rounded one
@@ -32,8 +27,6 @@ __device__ __forceinline__ double div_rn(double a, double b, double y) {
     r = __fma_rn(-q, b, a);
     return __fma_rn(r, y, q);
 }
-
-enum { KM_GLOBAL = 0, KM_LOCAL = 1, KM_REF = 2 };
 
 struct DevView {
     const uint4* occ;        // 5 planes x n_blocks entries {C[s] + count, bits[3]}: A, C, G, T, N (plane-major)
@@ -71,16 +64,6 @@ struct UnitSrc {
     uint32_t buf_bytes;       // per-wave staging buffer (bases)
     unsigned long long* ax_stats;  // diagnostic (speq_scan_reads_device_stats): k_scan_ax's work counters, else null
 };
-
-// Per-wave LDS: bases [buf_bytes] | qualities [buf_bytes] (local mode) | bad-mask words | N-mask words |
-// base bit-plane words (bit 0 of every base's 2-bit code, then bit 1; k-mer table scans).
-__host__ __device__ inline uint32_t staging_bytes(uint32_t k, uint32_t nwin) {
-    return ((2u * (64u * nwin + k)) + 63u) & ~63u;
-}
-__host__ __device__ inline uint32_t mask_words(uint32_t buf) { return buf / 64u + 1u; }
-__host__ __device__ inline uint32_t wave_lds_bytes(uint32_t buf, bool local) {
-    return buf * (local ? 2u : 1u) + 32u * mask_words(buf);
-}
 
 __device__ __forceinline__ void wave_sync() {
     // Lanes of one wave exchange data through their wave-private LDS region: order the LDS writes before

@@ -191,6 +191,8 @@ __global__ __launch_bounds__(BLOCK_THREADS, (KT && NWIN == 1 && MODE == KM_GLOBA
     const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t G = I.G, k = src.k;
     // (+ 2 words: the workgroup's T and ambiguous units, flushed with the histogram: ax_scan.hip §4i)
+    // (hist_region_words / _bytes with totals, scan_plan.hpp, which the launch requests; typed out here because
+    // the call changes this kernel's register allocation)
     const uint32_t hist_words = LDS_HIST ? ((MODE == KM_GLOBAL) ? G : 2u * G) + 2u : 0u;
     const uint32_t hist_bytes = (hist_words * 8u + 15u) & ~15u;
     unsigned long long* hA = reinterpret_cast<unsigned long long*>(smem);
@@ -700,6 +702,8 @@ void k_scan_kt(DevView I, UnitSrc src, unsigned long long* __restrict__ out_a, d
     const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t G = I.G, k = src.k;
     // (+ 2 words: the workgroup's T and ambiguous units, flushed with the histogram: ax_scan.hip §4i)
+    // (hist_region_words / _bytes with totals, scan_plan.hpp, which the launch requests; typed out here because
+    // the call changes this kernel's register allocation)
     const uint32_t hist_words = LDS_HIST ? ((MODE == KM_GLOBAL) ? G : 2u * G) + 2u : 0u;
     const uint32_t hist_bytes = (hist_words * 8u + 15u) & ~15u;
     unsigned long long* hA = reinterpret_cast<unsigned long long*>(smem);
@@ -1172,51 +1176,23 @@ namespace {
 using namespace speq_dev;
 
 
-template <int MODE, bool PAIRED, bool LDS, bool KT>
-void allow_big_lds_kt() {
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan<MODE, PAIRED, LDS, 1, false, KT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan<MODE, PAIRED, LDS, 2, false, KT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if (MODE != KM_REF)
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan<MODE, PAIRED, LDS, 1, MODE != KM_REF, KT>),
+// The kernel of a k_scan / k_scan_kt variant (a, b, w: k_scan's arguments; k_scan_kt takes no b).
+template <int P>
+constexpr auto scan_kernel() {
+    constexpr speq::ScanVariant V = speq::ScanVariant::unpack(P);
+    if constexpr (V.family == speq::VARIANT_K_SCAN) return &k_scan<V.mode, V.paired, V.lds_hist, V.width, V.em, V.kt>;
+    else return &k_scan_kt<V.mode, V.paired, V.lds_hist, V.em, V.width, V.compact>;
+}
+
+// Every compiled k_scan and k_scan_kt may take 160 KiB of dynamic LDS (occupancy caps pad it). Eager, at device open:
+// the first call also loads this translation unit's code object.
+void grant_big_lds() {
+    auto grant = [](auto packed) {
+        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(scan_kernel<decltype(packed)::value>()),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if (KT && MODE == KM_GLOBAL)
-        HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan<MODE, PAIRED, LDS, 4, false, KT>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-}
-
-template <int MODE, bool PAIRED, bool LDS, bool CK>
-void allow_big_lds_ktp() {
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan_kt<MODE, PAIRED, LDS, false, 1, CK>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan_kt<MODE, PAIRED, LDS, false, 2, CK>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan_kt<MODE, PAIRED, LDS, true, 1, CK>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-}
-
-template <int MODE, bool PAIRED, bool LDS>
-void allow_big_lds() {
-    allow_big_lds_kt<MODE, PAIRED, LDS, false>();
-    allow_big_lds_kt<MODE, PAIRED, LDS, true>();
-    if constexpr (MODE != KM_REF) {
-        allow_big_lds_ktp<MODE, PAIRED, LDS, false>();
-        allow_big_lds_ktp<MODE, PAIRED, LDS, true>();
-    }
-}
-
-void allow_big_lds_all() {
-    allow_big_lds<KM_GLOBAL, false, true>();
-    allow_big_lds<KM_GLOBAL, false, false>();
-    allow_big_lds<KM_GLOBAL, true, true>();
-    allow_big_lds<KM_GLOBAL, true, false>();
-    allow_big_lds<KM_LOCAL, false, true>();
-    allow_big_lds<KM_LOCAL, false, false>();
-    allow_big_lds<KM_LOCAL, true, true>();
-    allow_big_lds<KM_LOCAL, true, false>();
-    allow_big_lds<KM_REF, false, true>();
-    allow_big_lds<KM_REF, false, false>();
+    };
+    speq::for_each_compiled<speq::VARIANT_K_SCAN>(grant);
+    speq::for_each_compiled<speq::VARIANT_K_SCAN_KT>(grant);
 }
 
 // The q-mer table level for a scan of k-mers: the longest of q, q-1, q-2 that leaves a number of symbols divisible
@@ -1445,113 +1421,54 @@ const speq_device_index::KmerTable* ensure_ktab(speq_device_index* d, uint32_t k
     return it->second.table ? &it->second : nullptr;  // null table: too large, LF steps
 }
 
-// One launch of k_scan_kt / k_scan; each returns the instantiation it launched (tuning key "last_variant"), packed
-// from the template arguments of the launch itself.
-template <int MODE, bool PAIRED, bool LDS, bool EM, int NW, bool CK>
-int launch_kt_one(const DevView& v, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st,
-                  unsigned long long* a, double* w) {
-    hipLaunchKernelGGL((k_scan_kt<MODE, PAIRED, LDS, EM, NW, CK>), dim3(grid), dim3(BLOCK_THREADS), lds, st, v, src, a,
-                       w);
-    return speq::scan_variant(speq::VARIANT_K_SCAN_KT, MODE, PAIRED, LDS, EM, NW, false, CK);
-}
+// Launches the scan the plan of its facts chooses (scan_plan.hpp) and returns the plan's kernel ("last_kernel" codes),
+// or -1, nothing launched, for the diagnostic twin (src.ax_stats) when k_scan_ax cannot take the scan. The facts are
+// gathered in a fixed order that builds nothing a scan does not need: the anchor structures first (read scans), the
+// k-mer table only when the anchor kernel does not take the scan.
+int launch_scan(speq_device_index* d, int mode, bool paired, UnitSrc src, hipStream_t st, unsigned long long* a,
+                unsigned long long* b, double* w) {
+    speq::ScanFacts f;
+    f.mode = mode, f.paired = paired, f.em = src.em_mult != nullptr, f.stats = src.ax_stats != nullptr;
+    f.k = src.k, f.G = d->G, f.units = mode == KM_REF ? src.total_windows : src.n_units;
+    f.ilp = d->ilp, f.ilp_local = d->ilp_local, f.ilp_kt = d->ilp_kt, f.kt_pipeline = d->kt_pipeline;
+    f.blocks_per_cu = d->blocks_per_cu, f.blocks_per_cu_kt = d->blocks_per_cu_kt;
+    f.blocks_per_cu_ax = d->blocks_per_cu_ax;
+    f.grid_blocks = d->grid_blocks, f.grid_blocks_kt = d->grid_blocks_kt, f.grid_blocks_ax = d->grid_blocks_ax;
+    f.ax_generations = d->ax_generations, f.n_cus = d->n_cus;
+    const speq::AxTable* ax = mode != KM_REF ? speq::ax_facts(d, src, f) : nullptr;
+    if (!ax && src.ax_stats) return -1;  // the diagnostic twin exists for k_scan_ax only: launch nothing
+    const speq_device_index::KmerTable* kt = ax ? nullptr : ensure_ktab(d, src.k);
+    f.table = !kt ? speq::TABLE_NONE : kt->compact ? speq::TABLE_COMPACT : speq::TABLE_WIDE;
 
-template <int MODE, bool PAIRED, bool LDS, int NWIN, bool EM, bool KT>
-int launch_v_one(const DevView& v, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st,
-                 unsigned long long* a, unsigned long long* b, double* w) {
-    hipLaunchKernelGGL((k_scan<MODE, PAIRED, LDS, NWIN, EM, KT>), dim3(grid), dim3(BLOCK_THREADS), lds, st, v, src, a,
-                       b, w);
-    return speq::scan_variant(speq::VARIANT_K_SCAN, MODE, PAIRED, LDS, EM, NWIN, KT);
-}
-
-template <int MODE, bool PAIRED, bool LDS, bool CK>
-int launch_kt(const DevView& v, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st, unsigned long long* a,
-              double* w, uint32_t ilp) {
-    if (src.em_mult != nullptr) return launch_kt_one<MODE, PAIRED, LDS, true, 1, CK>(v, src, grid, lds, st, a, w);
-    if (ilp == 2) return launch_kt_one<MODE, PAIRED, LDS, false, 2, CK>(v, src, grid, lds, st, a, w);
-    return launch_kt_one<MODE, PAIRED, LDS, false, 1, CK>(v, src, grid, lds, st, a, w);
-}
-
-template <int MODE, bool PAIRED, bool LDS, bool KT>
-void launch_v(const speq_device_index* d, const DevView& v, const UnitSrc& src, uint32_t grid, size_t lds,
-              hipStream_t st, unsigned long long* a, unsigned long long* b, double* w) {
-    const uint32_t ilp = KT ? (d->ilp_kt ? d->ilp_kt : (v.kt_compact ? 1u : 2u))
-                            : (MODE == KM_LOCAL ? d->ilp_local : d->ilp);
-    int& variant = const_cast<speq_device_index*>(d)->last_variant;
-    if constexpr (KT && MODE != KM_REF) {
-        if (ilp <= 2 && d->kt_pipeline) {  // software-pipelined table scan
-            if (v.kt_compact) variant = launch_kt<MODE, PAIRED, LDS, true>(v, src, grid, lds, st, a, w, ilp);
-            else variant = launch_kt<MODE, PAIRED, LDS, false>(v, src, grid, lds, st, a, w, ilp);
-            return;
+    const speq::ScanPlan p = speq::plan_scan(f);
+    src.buf_bytes = p.buf_bytes;
+    if (ax) {
+        speq::launch_ax(d, *ax, p, src, st, a, w);
+    } else {
+        DevView v = scan_view(d, src.k);
+        if (p.table_read) {
+            v.ktab = kt->table;
+            v.kt_bmask = kt->compact ? kt->buckets : kt->buckets - 1;
+            v.kt_multi = kt->multi;
+            v.kt_compact = kt->compact ? 1u : 0u;
+            v.kt_k = src.k;
         }
+        const dim3 grid(p.grid), block(BLOCK_THREADS);
+        if (p.variant.family == speq::VARIANT_K_SCAN)
+            speq::with_variant<speq::VARIANT_K_SCAN>(p.variant, [&](auto packed) {
+                hipLaunchKernelGGL(scan_kernel<decltype(packed)::value>(), grid, block, p.lds_launch, st, v, src, a, b,
+                                   w);
+            });
+        else
+            speq::with_variant<speq::VARIANT_K_SCAN_KT>(p.variant, [&](auto packed) {
+                hipLaunchKernelGGL(scan_kernel<decltype(packed)::value>(), grid, block, p.lds_launch, st, v, src, a,
+                                   w);
+            });
     }
-    if (MODE != KM_REF && src.em_mult != nullptr)
-        variant = launch_v_one<MODE, PAIRED, LDS, 1, MODE != KM_REF, KT>(v, src, grid, lds, st, a, b, w);
-    else if (KT && MODE == KM_GLOBAL && ilp == 4)
-        variant = launch_v_one<MODE, PAIRED, LDS, 4, false, KT>(v, src, grid, lds, st, a, b, w);
-    else if (ilp >= 2)
-        variant = launch_v_one<MODE, PAIRED, LDS, 2, false, KT>(v, src, grid, lds, st, a, b, w);
-    else
-        variant = launch_v_one<MODE, PAIRED, LDS, 1, false, KT>(v, src, grid, lds, st, a, b, w);
-}
-
-template <int MODE, bool PAIRED, bool LDS>
-void launch_t(const speq_device_index* d, const UnitSrc& src, uint32_t grid, size_t lds, hipStream_t st,
-              unsigned long long* a, unsigned long long* b, double* w, const speq_device_index::KmerTable* kt) {
-    DevView v = scan_view(d, src.k);
-    // a compact table is read only by the pipelined table kernel; other scans of this k take LF steps
-    if (kt && kt->compact && !(MODE != KM_REF && d->ilp_kt <= 2 && d->kt_pipeline))
-        kt = nullptr;
-    if (kt) {
-        v.ktab = kt->table;
-        v.kt_bmask = kt->compact ? kt->buckets : kt->buckets - 1;
-        v.kt_multi = kt->multi;
-        v.kt_compact = kt->compact ? 1u : 0u;
-        v.kt_k = src.k;
-    }
-    if (MODE != KM_REF)
-        const_cast<speq_device_index*>(d)->last_kernel =
-            kt ? ((d->ilp_kt <= 2 && d->kt_pipeline) || kt->compact ? 2 : 1) : 0;
-    if (kt) launch_v<MODE, PAIRED, LDS, true>(d, v, src, grid, lds, st, a, b, w);
-    else launch_v<MODE, PAIRED, LDS, false>(d, v, src, grid, lds, st, a, b, w);
-}
-
-// returns the kernel it launched (speq_device_get_tuning "last_kernel" codes: 0 LF steps, 1/2 k-mer table, 3 ax)
-int launch_scan(speq_device_index* d, int mode, bool paired, const UnitSrc& src, uint64_t work_units,
-                hipStream_t st, unsigned long long* a, unsigned long long* b, double* w) {
-    // read scans: the anchor-and-extend kernel when the replica has (or can build) its structures for k (ax_scan.hip)
-    if (mode != KM_REF && speq::launch_ax(d, mode, paired, src, st, a, w)) {
-        d->last_kernel = 3;
-        return 3;
-    }
-    if (src.ax_stats) return -1;  // the diagnostic twin exists for k_scan_ax only: launch nothing
-    const speq_device_index::KmerTable* kt = ensure_ktab(d, src.k);
-    const bool lds_hist = d->G <= LDS_HIST_MAX_G;
-    const uint32_t hist_words = lds_hist ? ((mode == KM_GLOBAL) ? d->G : 2u * d->G) + 2u : 0u;
-    const size_t lds = ((hist_words * 8u + 15u) & ~15u) + (mode == KM_LOCAL ? QTAB_BYTES : 0u) +
-                       (size_t)WAVES_PER_BLOCK * wave_lds_bytes(src.buf_bytes, mode == KM_LOCAL);
-    // >= 4 units (or 256 windows) per wave; grid capped (default 4096 = 2x the 8 resident blocks x 256 CUs).
-    uint64_t blocks = (work_units + 4 * WAVES_PER_BLOCK - 1) / (4 * WAVES_PER_BLOCK);
-    if (blocks < 1) blocks = 1;
-    const uint32_t grid_cap = kt ? d->grid_blocks_kt : d->grid_blocks;
-    if (blocks > grid_cap) blocks = grid_cap;
-    size_t lds_launch = lds;
-    const uint32_t bpc = kt ? d->blocks_per_cu_kt : d->blocks_per_cu;
-    if (bpc > 0) {  // occupancy cap: pad dynamic LDS so only bpc blocks fit a CU
-        const size_t pad = (160u * 1024u) / bpc;
-        if (pad > lds_launch) lds_launch = pad & ~(size_t)15;
-    }
-    const uint32_t grid = (uint32_t)blocks;
-#define SPEQ_DISPATCH(M, P)                                                            \
-    do {                                                                               \
-        if (lds_hist) launch_t<M, P, true>(d, src, grid, lds_launch, st, a, b, w, kt); \
-        else launch_t<M, P, false>(d, src, grid, lds_launch, st, a, b, w, kt);         \
-    } while (0)
-    if (mode == KM_REF) SPEQ_DISPATCH(KM_REF, false);
-    else if (mode == KM_GLOBAL) { if (paired) SPEQ_DISPATCH(KM_GLOBAL, true); else SPEQ_DISPATCH(KM_GLOBAL, false); }
-    else { if (paired) SPEQ_DISPATCH(KM_LOCAL, true); else SPEQ_DISPATCH(KM_LOCAL, false); }
-#undef SPEQ_DISPATCH
+    d->last_variant.store(p.variant.pack(), std::memory_order_relaxed);
+    if (mode != KM_REF) d->last_kernel.store(p.last_kernel, std::memory_order_relaxed);  // the last *read* scan's
     HIP_OK(hipGetLastError());
-    return kt ? ((d->ilp_kt <= 2 && d->kt_pipeline) || kt->compact ? 2 : 1) : 0;
+    return p.last_kernel;
 }
 
 }  // namespace
@@ -1586,7 +1503,6 @@ static int scan_device_impl(speq_device_index* d, const uint8_t* d_seq, const ui
     src.end_adj = 0;
     src.k = p->k;
     src.cutoff = p->phred_cutoff;
-    src.buf_bytes = staging_bytes(p->k, std::max({d->ilp, d->ilp_local, d->ilp_kt ? d->ilp_kt : 2u}));
     src.ax_stats = ax_stats;
     const int mode = p->mode == SPEQ_MODE_LOCAL ? KM_LOCAL : KM_GLOBAL;
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1595,8 +1511,8 @@ static int scan_device_impl(speq_device_index* d, const uint8_t* d_seq, const ui
         HIP_OK(hipEventCreate(&e1));
         HIP_OK(hipEventRecord(e0, st));
     }
-    const int kernel = launch_scan(d, mode, p->paired != 0, src, p->paired ? n_reads / 2 : n_reads, st,
-                                   reinterpret_cast<unsigned long long*>(d_counts), nullptr, d_weights);
+    const int kernel = launch_scan(d, mode, p->paired != 0, src, st, reinterpret_cast<unsigned long long*>(d_counts),
+                                   nullptr, d_weights);
     if (d->timing) {
         if (kernel < 0) {  // nothing was launched (ax_stats, the anchor kernel cannot take it): no interval to time
             (void)hipEventDestroy(e0);
@@ -1772,7 +1688,7 @@ int speq_device_open(const speq_index* idx, int device, speq_device_index** out)
         // extra gathers in flight thrash the caches (cfg 3, n = 10 M: -15 %). profiles/r01/ab_occupancy.txt,
         // sweep_triples.jsonl
         d->ilp = fm.n < (4ull << 20) ? 2u : 1u;
-        allow_big_lds_all();
+        grant_big_lds();
         speq::startup_trace("device open: end");
         *out = d.release();
     });
@@ -2016,8 +1932,7 @@ uint64_t* launch_ref_shard(speq_device_index* d, uint32_t k, uint32_t shard, uin
     src.win_base = w0;
     src.end_adj = 1;
     src.k = k;
-    src.buf_bytes = staging_bytes(k, std::max(d->ilp, d->ilp_kt ? d->ilp_kt : 2u));
-    launch_scan(d, KM_REF, false, src, (w1 - w0 + 255) / 256, st, reinterpret_cast<unsigned long long*>(d_u_ref),
+    launch_scan(d, KM_REF, false, src, st, reinterpret_cast<unsigned long long*>(d_u_ref),
                 reinterpret_cast<unsigned long long*>(d_tot_ref), nullptr);
     return d_cum;
 }
@@ -2282,8 +2197,8 @@ int speq_device_get_tuning(const speq_device_index* d, const char* key, int64_t*
         else if (k == "kt_compact") *value = d->kt_compact ? 1 : 0;
         else if (k == "kt_load8") *value = d->kt_load8;
         else if (k == "ax_scan") *value = d->ax_scan ? 1 : 0;
-        else if (k == "last_kernel") *value = d->last_kernel;
-        else if (k == "last_variant") *value = d->last_variant;
+        else if (k == "last_kernel") *value = d->last_kernel.load(std::memory_order_relaxed);
+        else if (k == "last_variant") *value = d->last_variant.load(std::memory_order_relaxed);
         else if (k == "ax_mproof") *value = d->ax_mproof;
         else if (k == "ax_sproof") *value = d->ax_sproof;
         else if (k == "ax_load") *value = speq::ax_effective_load(d);

@@ -19,7 +19,8 @@ groups: global atomics) and asserts, per recipe:
 
 The last test asserts that the instantiations reported, all recipes together, are exactly ALL_VARIANTS. The inputs
 (tests/variant_inputs.py) hold ambiguous units, counted groups at the far end of the tally and multi-group rows on
-every read set, by the references alone (tests/test_variant_table_cpu.py). On the 2049-group replica the per-unit
+every read set, by the references alone (tests/test_variant_table_cpu.py). Every k_scan and k_scan_kt recipe then runs
+once more with its dynamic LDS padded to 160 KiB (the grant made at device open). On the 2049-group replica the per-unit
 report (33 set words), the FASTQ stream (2051 counters, GPU parser) and the instrumented twin's refusal are pinned
 too."""
 import ctypes as C
@@ -227,6 +228,43 @@ def test_the_recipes_reported_every_instantiation():
     unreached = sorted(str(v) for v in vt.ALL_VARIANTS - got)
     assert unreached == [], f"{len(unreached)} instantiations never launched: {unreached}"
     assert got == vt.ALL_VARIANTS
+
+
+# ---------------------------------------------------------------- more than 64 KiB of dynamic LDS
+@pytest.mark.parametrize("name", list(vt.REFS))
+def test_every_k_scan_and_k_scan_kt_instantiation_runs_with_160_kib_of_lds(name, replica):
+    """The grant of more than 64 KiB of dynamic LDS, made at device open for the set of compiled k_scan and k_scan_kt
+    instantiations: with "blocks_per_cu" and "blocks_per_cu_kt" at 1 every launch pads its LDS to 160 KiB, which a
+    kernel left out of the grant refuses. Every recipe of the plan that the anchor kernel does not take, once more:
+    (a) and (b), (c) in local mode, the counters alone for EM recipes, (e) for the pass."""
+    dev = replica(name)
+    mine = [r for r in vt.PLAN if r.ref == name and vt.predict(r).family != vt.K_SCAN_AX]
+    assert {vt.predict(r) for r in mine} == {v for v in vt.ALL_VARIANTS if v.family != vt.K_SCAN_AX
+                                             and v.lds_hist == (name == "g5")}
+    keys = ("blocks_per_cu", "blocks_per_cu_kt")
+    before = {key: dev.tuning(key) for key in keys}
+    try:
+        for r in mine:
+            set_tuning(dev, r)
+            dev.tune(**dict.fromkeys(keys, 1))
+            if r.entry == vt.REF:
+                u, t = dev.count_unique_kmers_per_group(r.k)
+                v = reported(dev, r)
+                ou, ot = vi.ref_unique(r.ref, r.k)
+                assert np.array_equal(u, ou) and np.array_equal(t, ot), f"{r.id} [{v}]: (U_ref, Tot_ref) differ"
+                continue
+            rd = vi.reads_of(r.ref, r.k, r.paired)
+            if r.entry == vt.EM:
+                em, got = em_scan(dev, r, rd)
+                em.close()
+            else:
+                got = dev.scan(rd.seq.tobytes(), rd.qual.tobytes(), rd.offsets, k=r.k, phred_cutoff=vi.CUTOFF,
+                               paired=r.paired, local=r.local)
+            v = reported(dev, r)
+            check_counters(r, v, got.total, got.ambiguous, got.unique, got.weights)
+    finally:
+        dev.tune(**before)
+        dev.tune(**vt.DEFAULTS)
 
 
 # ---------------------------------------------------------------- the other entry points at G = 2049

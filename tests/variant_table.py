@@ -1,10 +1,11 @@
 """The scan kernels' dispatch, restated by hand: which template instantiation every scan must launch.
 
-The three read-scan kernels are templates and the host dispatcher (launch_scan / launch_t / launch_v / launch_kt in
-scan_kernels.hip, launch_ax / ax_launch_mode / ax_launch_nwc in ax_scan.hip) picks one of about 200 separately
+The three read-scan kernels are templates and the host dispatcher (plan_scan and compiled() in scan_plan.hpp, from
+the facts launch_scan in scan_kernels.hip and ax_facts in ax_scan.hip gather) picks one of about 200 separately
 compiled instantiations from the scan's parameters. This file reads nothing from the library: `predict` is the rules
 written down again, `ALL_VARIANTS` the set the rules can produce, enumerated on its own, and `PLAN` one recipe or more
-per variant. tests/test_variant_table_cpu.py holds the three against each other without a GPU;
+per variant. tests/test_variant_table_cpu.py holds the three against each other without a GPU and
+tests/test_scan_plan_cpu.py holds the library's plan against them, also without one;
 tests/test_gpu_variants.py runs every recipe, asserts that the replica reports the predicted instantiation (tuning key
 "last_variant") and compares its results with the references.
 
