@@ -199,6 +199,40 @@ int speq_report_reads_device(speq_device_index* d, const uint8_t* d_seq, const u
 /* Host buffers, synchronous, staged in batches like speq_scan_reads. */
 int speq_report_reads(speq_device_index* d, const uint8_t* seq, const uint8_t* qual, const uint64_t* offsets,
                       uint64_t n_reads, const speq_scan_params* params, speq_read_report* reports, uint64_t* sets);
+/* ---- marker coverage (a diagnostic pass beside the scan) ----
+ * A marker of group g, at scan length k: a distinct N-free k-mer of the indexed texts (fwd and rc of every record)
+ * whose occurrences all lie in texts of g; a k-mer and its reverse complement are two markers. Its depth is the number
+ * of passing read windows equal to it (window filter and base conversion are the scan's; params->paired and
+ * params->mode are ignored). Per group: the markers, those of depth >= 1 (observed), the sum of depths (hits, equal to
+ * U[g] of a scan of the same reads), the largest depth, and depth_hist[j] = markers of depth exactly j for j < 7 and of
+ * depth >= 7 for j = 7. observed / markers is the breadth of coverage; a group that is really present shows a breadth
+ * near 1 - exp(-hits / markers), while copies of a few k-mers (an amplicon, duplicates, a contaminating fragment)
+ * give the same hits at a breadth near 0. Every passing window is searched exactly (no per-k structure), as in the
+ * per-unit report: an opt-in pass, not the hot path. The handle holds 4 bytes per SA position on the replica's GPU;
+ * the replica must outlive it. A marker's depth must stay below 2^31. The reference keeps none of this. */
+#define SPEQ_MARKER_BINS 8
+typedef struct {
+    uint64_t markers, observed, hits, max_depth, depth_hist[SPEQ_MARKER_BINS];
+} speq_marker_cov; /* 96 bytes */
+typedef struct speq_markers speq_markers;
+/* Fixes params->k (1 .. SPEQ_REPORT_MAX_K) and params->phred_cutoff, and marks the markers (one pass over the texts on
+ * the replica's GPU; blocking). SPEQ_E_NOMEM when the depth array does not fit the free HBM. */
+int speq_markers_create(speq_device_index* d, const speq_scan_params* params, speq_markers** out);
+/* Adds the reads' windows to the depths. Device buffers, asynchronous on stream; writes nothing but the handle's array.
+ * Reads of any length; n_reads == 0 launches nothing. */
+int speq_markers_add_reads_device(speq_markers* m, const uint8_t* d_seq, const uint8_t* d_qual,
+                                  const uint64_t* d_offsets, uint64_t n_reads, void* stream);
+/* Host buffers, synchronous, staged in batches like speq_report_reads; nothing is copied back. */
+int speq_markers_add_reads(speq_markers* m, const uint8_t* seq, const uint8_t* qual, const uint64_t* offsets,
+                           uint64_t n_reads);
+/* Waits for the adds of every stream of the device and folds the depths into out[G] (host, overwritten). The handle
+ * stays usable: more adds and another finalize give the totals of everything added so far. */
+int speq_markers_finalize(speq_markers* m, speq_marker_cov* out);
+/* Test accessor: every marker (depth 0 included) by ascending SA position. *n_markers (may be NULL) receives their
+ * number; lo / group / depth (any may be NULL) hold that many entries each: call once with null arrays for the size. */
+int speq_markers_list(speq_markers* m, uint64_t* n_markers, uint32_t* lo, uint32_t* group, uint32_t* depth);
+void speq_markers_free(speq_markers* m);
+
 /* ---- reference-uniqueness pass (replaces _async_count_unique_kmers_per_group, fm_scanner.cpp:1476-1576)
  * For every window of every text (fwd and rc of each record): Tot_ref[g] += 1, and U_ref[g] += 1 iff
  * every occurrence lies in a text of group g.  Outputs are host arrays of G u64 (overwritten). */
@@ -328,6 +362,11 @@ int speq_group_sets_get(const speq_group_sets* s, uint64_t i, uint64_t* words /*
 int speq_group_sets_totals(const speq_group_sets* s, uint64_t* units, uint64_t* passing, uint64_t* unique,
                            uint64_t* shared);
 void speq_group_sets_free(speq_group_sets* s);
+
+/* Marker coverage (speq_markers_*) of the whole of FASTQ file(s) (plain or gzip; both files' records when path2 != NULL) through a handle of its own:
+ * blocks parsed on host threads and added in any order, one finalize at the end into out[G]. stats may be NULL. */
+int speq_markers_fastq(speq_device_index* d, const char* path1, const char* path2, const speq_scan_params* params,
+                       uint32_t threads, speq_marker_cov* out, speq_stream_stats* stats);
 
 /* ---- several GPUs in one process ----
  * Reads shard across the GPUs of a node, the index is replicated (one speq_device_index per GPU, opened from the

@@ -54,6 +54,15 @@ class StreamStats(C.Structure):
     _fields_ = [("records", C.c_uint64), ("bases", C.c_uint64), ("batches", C.c_uint64), ("seconds", C.c_double)]
 
 
+MARKER_BINS = 8
+
+
+class MarkerCov(C.Structure):
+    _fields_ = [("markers", C.c_uint64), ("observed", C.c_uint64), ("hits", C.c_uint64), ("max_depth", C.c_uint64),
+                ("depth_hist", C.c_uint64 * MARKER_BINS)]
+
+
+_U32P = C.POINTER(C.c_uint32)
 SIGNATURES = {
     "speq_last_error": (C.c_char_p, []),
     "speq_abi_version": (C.c_int, []),
@@ -83,6 +92,14 @@ SIGNATURES = {
     "speq_group_sets_get": (C.c_int, [_P, C.c_uint64, _U64P, _U64P]),
     "speq_group_sets_totals": (C.c_int, [_P, _U64P, _U64P, _U64P, _U64P]),
     "speq_group_sets_free": (None, [_P]),
+    "speq_markers_create": (C.c_int, [_P, C.POINTER(ScanParams), C.POINTER(_P)]),
+    "speq_markers_add_reads_device": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P]),
+    "speq_markers_add_reads": (C.c_int, [_P, C.c_char_p, C.c_char_p, _U64P, C.c_uint64]),
+    "speq_markers_finalize": (C.c_int, [_P, _P]),
+    "speq_markers_list": (C.c_int, [_P, _U64P, _U32P, _U32P, _U32P]),
+    "speq_markers_fastq": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.POINTER(ScanParams), C.c_uint32, _P,
+                                     C.POINTER(StreamStats)]),
+    "speq_markers_free": (None, [_P]),
     "speq_ref_unique": (C.c_int, [_P, C.c_uint32, _U64P, _U64P]),
     "speq_ref_unique_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P]),
     "speq_comm_unique_id": (C.c_int, [_P]),

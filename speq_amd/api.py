@@ -20,10 +20,10 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import (SPEQ_MODE_GLOBAL, SPEQ_MODE_LOCAL, BuildOpts, IndexInfo, ScanParams, Slot, SpeqError,  # noqa: F401
-                   StreamStats, check, lib)
+from ._lib import (MARKER_BINS, SPEQ_MODE_GLOBAL, SPEQ_MODE_LOCAL, BuildOpts, IndexInfo, ScanParams, Slot,  # noqa: F401
+                   SpeqError, StreamStats, check, lib)
 
-__all__ = ["FmIndex", "DeviceIndex", "Node", "Pipeline", "ScanResult", "ReadReport", "Groupings", "EmHistogram", "Comm", "file_to_map", "unique_to_percent",
+__all__ = ["FmIndex", "DeviceIndex", "Node", "Pipeline", "ScanResult", "ReadReport", "Markers", "MarkerCoverage", "Groupings", "EmHistogram", "Comm", "file_to_map", "unique_to_percent",
            "em_refine", "pack_records", "SpeqError", "SPEQ_MODE_GLOBAL", "SPEQ_MODE_LOCAL"]
 
 
@@ -181,6 +181,39 @@ def _set_groups(words) -> frozenset:
 
 
 @dataclass
+class MarkerCoverage:
+    """Per-group marker coverage (speq_markers_finalize): a marker of group g is a distinct k-mer of the texts found
+    in g alone, its depth the number of passing read windows equal to it."""
+    markers: np.ndarray      # markers of the group (uint64)
+    observed: np.ndarray     # markers of depth >= 1 (uint64)
+    hits: np.ndarray         # sum of depths: the scan's U[g] (uint64)
+    max_depth: np.ndarray    # largest depth (uint64)
+    depth_hist: np.ndarray   # [G, 8] uint64: markers of depth exactly j for j < 7, of depth >= 7 for j = 7
+
+    @classmethod
+    def from_records(cls, rec: np.ndarray) -> "MarkerCoverage":
+        """rec: [G, 12] uint64, the speq_marker_cov records."""
+        return cls(rec[:, 0].copy(), rec[:, 1].copy(), rec[:, 2].copy(), rec[:, 3].copy(), rec[:, 4:].copy())
+
+    @property
+    def breadth(self) -> np.ndarray:
+        """observed / markers (nan for a group without markers)."""
+        with np.errstate(all="ignore"):
+            return np.where(self.markers > 0, self.observed / np.maximum(self.markers, 1).astype(np.float64), np.nan)
+
+    @property
+    def mean_depth(self) -> np.ndarray:
+        with np.errstate(all="ignore"):
+            return np.where(self.markers > 0, self.hits / np.maximum(self.markers, 1).astype(np.float64), np.nan)
+
+    @property
+    def expected_breadth(self) -> np.ndarray:
+        """1 - exp(-hits / markers): the breadth that uniform sampling at this depth would give; the figure to hold
+        `breadth` against (nan for a group without markers)."""
+        return 1.0 - np.exp(-self.mean_depth)
+
+
+@dataclass
 class ScanResult:
     total: int               # T: passing windows
     ambiguous: int           # reads (or pairs) whose counted windows name >= 2 groups
@@ -274,6 +307,26 @@ class DeviceIndex:
         finally:
             lib().speq_group_sets_free(h)
         return out, totals
+
+    def marker_coverage(self, seq: bytes, qual: bytes, offsets: np.ndarray, k: int,
+                        phred_cutoff: int = 30) -> MarkerCoverage:
+        """Marker coverage of host reads (speq_markers_*): one handle, one add, one finalize. A diagnostic pass, far
+        slower than scan()."""
+        m = Markers(self, k, phred_cutoff)
+        try:
+            m.add(seq, qual, offsets)
+            return m.finalize()
+        finally:
+            m.close()
+
+    def marker_coverage_fastq(self, path1: str, path2: Optional[str] = None, k: int = 21, phred_cutoff: int = 30,
+                              threads: int = 4) -> MarkerCoverage:
+        """Marker coverage of FASTQ(.gz) file(s) (speq_markers_fastq; both files' records when path2 is given)."""
+        p = ScanParams(k, phred_cutoff, int(path2 is not None), SPEQ_MODE_GLOBAL)
+        rec = np.zeros((self.n_groups, 4 + MARKER_BINS), dtype=np.uint64)
+        check(lib().speq_markers_fastq(self._h, path1.encode(), path2.encode() if path2 else None, C.byref(p), threads,
+                                       rec.ctypes.data, None))
+        return MarkerCoverage.from_records(rec)
 
     AX_STATS_KEYS = ("wave_iters", "lookup_lanes", "run_lanes", "lookup_waves", "run_waves", "run_windows",
                      "deferred", "filter_pass", "p2_probes", "p2_verify", "chunks", "segments", "qual_bytes",
@@ -379,6 +432,54 @@ class DeviceIndex:
     def close(self):
         if self._h:
             lib().speq_device_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Markers:
+    """Depth of every marker of a replica at one k (speq_markers_*): create marks the markers, add / add_device count
+    the reads' windows on them, finalize folds the depths per group and may be called again after more adds."""
+
+    def __init__(self, dev: DeviceIndex, k: int, phred_cutoff: int = 30):
+        self.dev = dev
+        self.n_groups = dev.n_groups
+        p = ScanParams(k, phred_cutoff, 0, SPEQ_MODE_GLOBAL)
+        h = C.c_void_p()
+        check(lib().speq_markers_create(dev.handle, C.byref(p), C.byref(h)))
+        self._h = h
+
+    def add(self, seq: bytes, qual: bytes, offsets: np.ndarray) -> None:
+        """Host reads (staged to HBM in batches; synchronous)."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        check(lib().speq_markers_add_reads(self._h, seq, qual, _u64p(off), len(off) - 1))
+
+    def add_device(self, d_seq: int, d_qual: int, d_offsets: int, n_reads: int, stream: int = 0) -> None:
+        """HBM-resident reads (raw device pointers, like DeviceIndex.scan_device); asynchronous on `stream`."""
+        check(lib().speq_markers_add_reads_device(self._h, d_seq, d_qual, d_offsets, n_reads, stream or None))
+
+    def finalize(self) -> MarkerCoverage:
+        rec = np.zeros((self.n_groups, 4 + MARKER_BINS), dtype=np.uint64)
+        check(lib().speq_markers_finalize(self._h, rec.ctypes.data))
+        return MarkerCoverage.from_records(rec)
+
+    def list(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Test accessor (speq_markers_list): (lo, group, depth) of every marker, ascending SA position."""
+        n = C.c_uint64()
+        check(lib().speq_markers_list(self._h, C.byref(n), None, None, None))
+        lo, grp, dep = (np.zeros(n.value, dtype=np.uint32) for _ in range(3))
+        u32p = C.POINTER(C.c_uint32)
+        check(lib().speq_markers_list(self._h, None, lo.ctypes.data_as(u32p), grp.ctypes.data_as(u32p),
+                                      dep.ctypes.data_as(u32p)))
+        return lo, grp, dep
+
+    def close(self):
+        if self._h:
+            lib().speq_markers_free(self._h)
             self._h = None
 
     def __del__(self):

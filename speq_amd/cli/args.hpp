@@ -37,6 +37,7 @@ struct CmdArguments {  // include/arg_parse.h:10-28
     std::vector<int> devices;    // --devices: explicit GPU ordinals (repeats = logical shards of one GPU)
     unsigned int max_em_iterations{1000};
     std::filesystem::path out_file_group_sets{};  // --group-sets: the pairs' (reads') group sets, the real fusion map
+    std::filesystem::path out_file_marker_coverage{};  // --marker-coverage: per group, its markers and their depths
 };
 
 struct ParseError : std::runtime_error {

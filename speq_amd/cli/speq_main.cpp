@@ -59,6 +59,10 @@ const char* HELP =
     "      --group-sets FILE     scan: after the scan, one more pass over the reads writes FILE: one line per distinct\n"
     "                            set of groups that a read's (pair's) unique k-mers name, as units, number of groups,\n"
     "                            names ('-' = none); the lines of 2 or more groups are the fusion map\n"
+    "      --marker-coverage FILE scan: after the scan, one more pass over the reads writes FILE: per group, how many of\n"
+    "                            its unique k-mers (markers) the reads cover and how deep: name, markers, observed,\n"
+    "                            breadth, hits, mean_depth, expected_breadth, max_depth, d0..d7 (tab-separated); a\n"
+    "                            breadth far below expected_breadth means copies of few k-mers, not the variant\n"
     "one process per GPU: run under a launcher that sets WORLD_SIZE > 1, RANK and LOCAL_RANK (e.g. torchrun\n"
     "--no-python bin/speq scan ...): each rank scans its share of the reads on GPU $LOCAL_RANK and the counts are\n"
     "summed with RCCL; rank 0 prints and writes the results ($SPEQ_RENDEZVOUS: the id file, default under /tmp)\n";
@@ -154,6 +158,7 @@ CmdArguments parse(int argc, char** argv) {
             }
         }
         else if (allow_reads && opt == "--group-sets") a.out_file_group_sets = value();
+        else if (allow_reads && opt == "--marker-coverage") a.out_file_marker_coverage = value();
         else if (allow_reads && opt == "--max-em-iterations") a.max_em_iterations = to_number<unsigned>(opt, value());
         else throw ParseError("Unknown option " + opt + ". In case this is meant to be a non-option/argument/parameter, "
                               "please specify the start of non-options with '--'.");
@@ -187,6 +192,7 @@ CmdArguments parse(int argc, char** argv) {
     }
     check_out_file(a.out_file_path, a.is_force);
     if (!a.out_file_group_sets.empty()) check_out_file(a.out_file_group_sets, a.is_force);
+    if (!a.out_file_marker_coverage.empty()) check_out_file(a.out_file_marker_coverage, a.is_force);
     a.is_parsed = true;
     return a;
 }
@@ -516,6 +522,39 @@ void write_group_sets(const CmdArguments& a, speq_device_index* d, const speq_sc
     }
 }
 
+// FILE of --marker-coverage: a header line, then per group (groupings order) its name, markers, observed,
+// breadth = observed / markers, hits, mean_depth = hits / markers, expected_breadth = 1 - exp(-mean_depth) (the breadth
+// uniform sampling at that depth would give), max_depth and the eight depth bins; the ratios are "-" without markers.
+void write_marker_coverage(const CmdArguments& a, speq_device_index* d, const speq_scan_params& prm,
+                           const std::vector<std::string>& names) {
+    std::vector<speq_marker_cov> cov(names.size());
+    ok(speq_markers_fastq(d, a.in_file_reads_path_1.c_str(),
+                          a.in_file_reads_path_2.empty() ? nullptr : a.in_file_reads_path_2.c_str(), &prm, a.threads,
+                          cov.data(), nullptr),
+       "marker coverage");
+    std::ofstream of(a.out_file_marker_coverage);
+    if (!of) throw CApiError("cannot write " + a.out_file_marker_coverage.string());
+    of << "name\tmarkers\tobserved\tbreadth\thits\tmean_depth\texpected_breadth\tmax_depth";
+    for (int j = 0; j < SPEQ_MARKER_BINS; ++j) of << "\td" << j;
+    of << "\n";
+    auto ratio = [](double x) {
+        char buf[64];
+        std::snprintf(buf, sizeof buf, "%.6f", x);
+        return std::string(buf);
+    };
+    for (size_t g = 0; g < names.size(); ++g) {
+        const speq_marker_cov& c = cov[g];
+        const bool has = c.markers > 0;
+        const double mean = has ? (double)c.hits / (double)c.markers : 0.0;
+        of << names[g] << "\t" << c.markers << "\t" << c.observed << "\t"
+           << (has ? ratio((double)c.observed / (double)c.markers) : std::string("-")) << "\t" << c.hits << "\t"
+           << (has ? ratio(mean) : std::string("-")) << "\t" << (has ? ratio(1.0 - std::exp(-mean)) : std::string("-"))
+           << "\t" << c.max_depth;
+        for (int j = 0; j < SPEQ_MARKER_BINS; ++j) of << "\t" << c.depth_hist[j];
+        of << "\n";
+    }
+}
+
 int run_scan(CmdArguments& a) {
     PhaseClock phase;
     Dist dd = dist_from_env(a);
@@ -768,6 +807,12 @@ int run_scan(CmdArguments& a) {
     if (!a.out_file_group_sets.empty()) {
         write_group_sets(a, d, prm, h.names);
         phase("group sets");
+    }
+    // --marker-coverage: one more pass over the same reads, placed like --group-sets (first replica, whole file, after
+    // everything else the run prints and writes).
+    if (!a.out_file_marker_coverage.empty()) {
+        write_marker_coverage(a, d, prm, h.names);
+        phase("marker coverage");
     }
     // The device replica, its pinned pipeline slots and the index are left to process exit: unpinning and freeing
     // them explicitly costs ~0.07 s and the process ends right after this.

@@ -888,6 +888,22 @@ struct ReportSink final : HostSink {
     }
 };
 
+// Marker coverage of every host-parsed block (speq_markers_add_reads) into one handle: the depths stay on the device, so
+// nothing comes back per block and the blocks' order does not matter (integer adds).
+struct MarkerSink final : HostSink {
+    speq_markers* m;
+    explicit MarkerSink(speq_markers* handle) : m(handle) {}
+    void submit(const speq_slot& s, uint64_t records) override {
+        struct Release {
+            MarkerSink& sink;
+            int32_t slot;
+            ~Release() { sink.release(slot); }
+        } rel{*this, s.slot};
+        if (records == 0) return;
+        check_rc(speq_markers_add_reads(m, s.seq, s.qual, s.offsets, records));
+    }
+};
+
 // Pinned slot size of speq_scan_fastq's pipeline: a block pair of up to 12 MiB per file plus one record usually
 // fits (larger blocks grow their slot once: speq_pipeline_reserve).
 constexpr uint64_t SLOT_BYTES = 16ull << 20;
@@ -1535,6 +1551,35 @@ extern "C" int speq_report_fastq(speq_device_index* d, const char* path1, const 
         }
         *out = res.release();
     });
+}
+
+extern "C" int speq_markers_fastq(speq_device_index* d, const char* path1, const char* path2,
+                                  const speq_scan_params* params, uint32_t threads, speq_marker_cov* out,
+                                  speq_stream_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = speq::guarded([&] {
+        if (!params) throw std::invalid_argument("speq_markers_fastq: null params");
+        if (params->k < 1 || params->k > SPEQ_REPORT_MAX_K)
+            throw std::invalid_argument("speq_markers_fastq: k must be in [1, 1024]");
+        if (!d || !path1 || !out) throw std::invalid_argument("speq_markers_fastq: null argument");
+    });
+    if (rc != SPEQ_OK) return rc;
+    speq_markers* m = nullptr;
+    rc = speq_markers_create(d, params, &m);  // (its own status: SPEQ_E_NOMEM when the depth array does not fit)
+    if (rc != SPEQ_OK) return rc;
+    rc = speq::guarded([&] {
+        MarkerSink sink(m);
+        const StreamTotals tot = run_stream(path1, path2, threads, sink, false, false);
+        check_rc(speq_markers_finalize(m, out));
+        if (stats) {
+            stats->records = tot.records;
+            stats->bases = tot.bases;
+            stats->batches = tot.batches;
+            stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+    });
+    speq_markers_free(m);
+    return rc;
 }
 
 extern "C" uint64_t speq_group_sets_count(const speq_group_sets* s) { return s ? s->units.size() : 0; }

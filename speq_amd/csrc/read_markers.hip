@@ -1,0 +1,427 @@
+// Marker coverage (speq_markers_*): how many of each group's markers the reads cover, and how deep. A
+// marker of group g is a distinct N-free k-mer of the indexed texts whose occurrences all lie in texts of g; it is
+// named by the start `lo` of its SA interval. The handle keeps one u32 per SA position: bit 31 marks a marker (set by
+// one pass over the texts at create), bits 0..30 count the passing read windows equal to it. A diagnostic pass beside
+// the scan kernels, shaped like the per-unit report (read_report.hip): every passing window gets an exact backward
+// search (search_lds), no per-k structure is used, and nothing here is on the hot path of `speq scan`.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <memory>
+#include <mutex>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "capi_internal.hpp"
+#include "device_index.hpp"
+#include "scan_device.hpp"
+
+struct speq_markers {
+    speq_device_index* dev = nullptr;
+    speq_scan_params params{};  // k and phred_cutoff, fixed at create
+    uint64_t n = 0;             // SA positions
+    uint32_t G = 0;
+    uint32_t* d_depth = nullptr;  // [n]: MARK | depth
+};
+
+namespace {
+
+using namespace speq_dev;
+
+constexpr uint32_t MARK = 0x80000000u;        // bit 31 of a depth word: the position starts a marker's interval
+constexpr uint32_t LDS_TALLY_GROUPS = 512u;   // the fold tallies in LDS up to this many groups (26 KiB), else in HBM
+constexpr uint32_t COV_WORDS = sizeof(speq_marker_cov) / 8;  // u64 words of one group's record
+// per-block tally of the fold, per group: u64 hits, then u32 {markers, observed, max_depth, bins[8]}
+constexpr uint32_t TALLY_U32 = 3u + SPEQ_MARKER_BINS;
+__host__ __device__ inline uint32_t tally_bytes(uint32_t G) { return G * (8u + 4u * TALLY_U32); }
+
+struct OutOfDeviceMemory : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+
+void dev_alloc(void** p, size_t bytes, const char* who) {
+    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        throw OutOfDeviceMemory(std::string(who) + ": out of device memory (" + std::to_string(bytes) + " bytes)");
+    }
+    if (e != hipSuccess) throw speq::DeviceError(std::string(who) + ": hipMalloc: " + hipGetErrorString(e));
+}
+
+// guarded() with the device allocations' failure as SPEQ_E_NOMEM
+template <typename F>
+int guarded_nomem(F&& f) {
+    int nomem = 0;
+    std::string msg;
+    const int rc = speq::guarded([&] {
+        try {
+            f();
+        } catch (const OutOfDeviceMemory& e) {
+            nomem = 1;
+            msg = e.what();
+        }
+    });
+    if (!nomem) return rc;
+    speq::set_last_error(msg);
+    return SPEQ_E_NOMEM;
+}
+
+// Per-wave LDS: u16 prefix counts of bad positions [64 + k] | symbol codes [64 + k - 1], rounded to 16 B (the
+// report's layout).
+__host__ __device__ inline uint32_t marker_wave_bytes(uint32_t k) { return (3u * (64u + k) + 15u) & ~15u; }
+
+// One tile of 64 window starts over `span` staged positions (span <= 64 + k - 1): at(p) gives position p's symbol
+// code (0..3, or 4 for anything that ends a window) and whether it is bad; the wave's region then holds each symbol
+// and the number of bad positions before it, so window j passes iff cnt[j + k] == cnt[j]. Lane j searches window j
+// (has: window j exists; then j + k <= span) and returns the search's result with the interval start in `lo`.
+template <class At>
+__device__ __forceinline__ int search_tile(const DevView& I, const Rsrc& R, unsigned char* sym, uint16_t* cnt,
+                                           uint32_t span, uint32_t k, bool has, uint32_t lane, uint32_t& lo, At&& at) {
+    const uint64_t below = (1ull << lane) - 1ull;
+    uint32_t bad_before = 0;
+    for (uint32_t c = 0; c < span; c += 64u) {
+        const uint32_t p = c + lane;
+        const bool valid = p < span;
+        uint32_t s = 4u;
+        bool bad = false;
+        if (valid) at(p, s, bad);
+        const uint64_t bal = __ballot(bad);
+        if (valid) {
+            sym[p] = (unsigned char)s;
+            cnt[p] = (uint16_t)(bad_before + (uint32_t)__popcll(bal & below));
+        }
+        bad_before += (uint32_t)__popcll(bal);
+    }
+    if (lane == 0) cnt[span] = (uint16_t)bad_before;
+    wave_sync();
+    int res = -1;
+    if (has && cnt[lane + k] == cnt[lane]) {
+        uint32_t hi;
+        res = search_lds(I, R, sym + lane, k, true, lo, hi);
+    }
+    wave_sync();  // the next tile restages this wave's region
+    return res;
+}
+
+// Read pass: one wave64 per read, tiles of 64 window starts. A window whose k-mer lies in one group adds 1 to the
+// depth word at its interval start: a no-return atomic, one per lane (adjacent windows have different starts).
+__global__ __launch_bounds__(BLOCK_THREADS) void k_marker_reads(const DevView I, const uint8_t* __restrict__ seq,
+                                                                const uint8_t* __restrict__ qual,
+                                                                const uint64_t* __restrict__ off, uint64_t n_reads,
+                                                                uint32_t k, uint32_t cutoff,
+                                                                uint32_t* __restrict__ depth) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    unsigned char* base = lds + wave * marker_wave_bytes(k);
+    uint16_t* cnt = reinterpret_cast<uint16_t*>(base);
+    unsigned char* sym = base + 2u * (64u + k);
+    const Rsrc R = make_rsrc(I);
+    for (uint64_t r = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave; r < n_reads;
+         r += (uint64_t)gridDim.x * WAVES_PER_BLOCK) {
+        const uint64_t beg = off[r], len = off[r + 1] - beg;
+        if (len < k) continue;
+        const uint64_t nwin = len - k + 1u;
+        for (uint64_t tile = 0; tile < nwin; tile += 64u) {
+            const uint32_t span = (uint32_t)min((uint64_t)(64u + k - 1u), len - tile);
+            uint32_t lo = 0;
+            const int res = search_tile(I, R, sym, cnt, span, k, tile + lane < nwin, lane, lo,
+                                        [&](uint32_t p, uint32_t& s, bool& bad) {
+                                            const uint64_t at = beg + tile + p;
+                                            s = ascii_sym(seq[at]);
+                                            const int32_t q = min(max((int32_t)qual[at] - 33, 0), 41);
+                                            bad = s == 4u || (uint32_t)q <= cutoff;
+                                        });
+            if (res >= 0 && lo < I.n) atomicAdd(&depth[lo], 1u);
+        }
+    }
+}
+
+// Marker pass: the same search over every window of the FM text (SA-alphabet codes: A..T = 2..5; separators, the
+// terminator and N end a window, so a window of A, C, G, T only lies wholly inside one text). One wave per tile of 64
+// text positions; a single-group result marks its interval start.
+__global__ __launch_bounds__(BLOCK_THREADS) void k_marker_texts(const DevView I, const uint8_t* __restrict__ text,
+                                                                uint32_t k, uint32_t* __restrict__ depth) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    unsigned char* base = lds + wave * marker_wave_bytes(k);
+    uint16_t* cnt = reinterpret_cast<uint16_t*>(base);
+    unsigned char* sym = base + 2u * (64u + k);
+    const Rsrc R = make_rsrc(I);
+    const uint64_t n = I.n;
+    if (n < k) return;
+    const uint64_t nwin = n - k + 1u;
+    for (uint64_t tile = ((uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave) * 64u; tile < nwin;
+         tile += (uint64_t)gridDim.x * WAVES_PER_BLOCK * 64u) {
+        const uint32_t span = (uint32_t)min((uint64_t)(64u + k - 1u), n - tile);
+        uint32_t lo = 0;
+        const int res = search_tile(I, R, sym, cnt, span, k, tile + lane < nwin, lane, lo,
+                                    [&](uint32_t p, uint32_t& s, bool& bad) {
+                                        const uint32_t c = text[tile + p];
+                                        bad = c < 2u || c > 5u;
+                                        s = bad ? 4u : c - 2u;
+                                    });
+        if (res >= 0 && lo < I.n) atomicOr(&depth[lo], MARK);
+    }
+}
+
+__device__ __forceinline__ uint32_t depth_bin(uint32_t dp) { return min(dp, (uint32_t)SPEQ_MARKER_BINS - 1u); }
+
+// Fold: grid-stride over SA positions; a marked position's group is that of the one-position interval [i, i + 1).
+// LDS_TALLY: the block tallies in LDS and flushes its non-zero words once; else every marker goes to HBM atomics.
+template <bool LDS_TALLY>
+__global__ __launch_bounds__(256) void k_marker_fold(const DevView I, const uint32_t* __restrict__ depth,
+                                                     unsigned long long* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const uint32_t G = I.G;
+    unsigned long long* t_hits = reinterpret_cast<unsigned long long*>(lds);
+    uint32_t* t_w = reinterpret_cast<uint32_t*>(lds + 8u * (LDS_TALLY ? G : 0u));
+    if (LDS_TALLY) {
+        for (uint32_t i = threadIdx.x; i < G; i += blockDim.x) t_hits[i] = 0ull;
+        for (uint32_t i = threadIdx.x; i < G * TALLY_U32; i += blockDim.x) t_w[i] = 0u;
+        __syncthreads();
+    }
+    const Rsrc R = make_rsrc(I);
+    const uint64_t n = I.n;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t w = depth[i];
+        if (!(w & MARK)) continue;
+        const int g = classify(I, R, (uint32_t)i, (uint32_t)i + 1u);
+        if (g < 0 || (uint32_t)g >= G) continue;
+        const uint32_t dp = w & ~MARK;
+        if (LDS_TALLY) {
+            uint32_t* t = t_w + (uint32_t)g * TALLY_U32;
+            atomicAdd(&t[0], 1u);
+            if (dp) {
+                atomicAdd(&t[1], 1u);
+                atomicMax(&t[2], dp);
+                atomicAdd(&t_hits[g], (unsigned long long)dp);
+            }
+            atomicAdd(&t[3u + depth_bin(dp)], 1u);
+        } else {
+            unsigned long long* o = out + (uint64_t)g * COV_WORDS;
+            atomicAdd(&o[0], 1ull);
+            if (dp) {
+                atomicAdd(&o[1], 1ull);
+                atomicAdd(&o[2], (unsigned long long)dp);
+                atomicMax(&o[3], (unsigned long long)dp);
+            }
+            atomicAdd(&o[4u + depth_bin(dp)], 1ull);
+        }
+    }
+    if (LDS_TALLY) {
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < G * TALLY_U32; i += blockDim.x) {
+            const uint32_t v = t_w[i];
+            if (!v) continue;
+            const uint32_t g = i / TALLY_U32, f = i - g * TALLY_U32;
+            unsigned long long* o = out + (uint64_t)g * COV_WORDS;
+            if (f == 2u) atomicMax(&o[3], (unsigned long long)v);
+            else atomicAdd(&o[f < 2u ? f : f + 1u], (unsigned long long)v);  // markers, observed | bins at 4..
+        }
+        for (uint32_t g = threadIdx.x; g < G; g += blockDim.x)
+            if (t_hits[g]) atomicAdd(&out[(uint64_t)g * COV_WORDS + 2u], t_hits[g]);
+    }
+}
+
+// speq_markers_list: the group of every marked position (0xFFFFFFFF elsewhere)
+__global__ __launch_bounds__(256) void k_marker_groups(const DevView I, const uint32_t* __restrict__ depth,
+                                                       uint32_t* __restrict__ group) {
+    const Rsrc R = make_rsrc(I);
+    const uint64_t n = I.n;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        group[i] = (depth[i] & MARK) ? (uint32_t)classify(I, R, (uint32_t)i, (uint32_t)i + 1u) : 0xFFFFFFFFu;
+}
+
+struct DevBuf {
+    void* p = nullptr;
+    DevBuf(size_t bytes, const char* who) { dev_alloc(&p, bytes, who); }
+    ~DevBuf() { (void)hipFree(p); }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+};
+
+void check_create(const speq_device_index* d, const speq_scan_params* p, speq_markers** out) {
+    const char* who = "speq_markers_create";
+    if (!p) throw std::invalid_argument(std::string(who) + ": null params");
+    if (p->k < 1 || p->k > SPEQ_REPORT_MAX_K) throw std::invalid_argument(std::string(who) + ": k must be in [1, 1024]");
+    if (!d) throw std::invalid_argument(std::string(who) + ": null device index");
+    if (!out) throw std::invalid_argument(std::string(who) + ": null output");
+}
+
+uint32_t grid_1d(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 16384u)); }
+
+void create_impl(speq_device_index* d, const speq_scan_params* p, speq_markers** out) {
+    check_create(d, p, out);
+    DeviceGuard g(d->device);
+    auto m = std::make_unique<speq_markers>();
+    m->dev = d;
+    m->params = *p;
+    m->n = d->view.n;
+    m->G = d->G;
+    dev_alloc(reinterpret_cast<void**>(&m->d_depth), m->n * 4, "speq_markers_create");
+    try {
+        hipStream_t st = d->stream;
+        HIP_OK(hipMemsetAsync(m->d_depth, 0, m->n * 4, st));
+        const DevView v = speq::search_view(d, p->k);
+        const uint64_t tiles = m->n >= p->k ? (m->n - p->k + 1 + 63) / 64 : 0;
+        if (tiles) {
+            const uint64_t blocks = std::min<uint64_t>((tiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 16384u);
+            hipLaunchKernelGGL(k_marker_texts, dim3((uint32_t)blocks), dim3(BLOCK_THREADS),
+                               (size_t)WAVES_PER_BLOCK * marker_wave_bytes(p->k), st, v, d->d_text, p->k, m->d_depth);
+            HIP_OK(hipGetLastError());
+        }
+        // the adds come on the callers' streams: the marks are complete before the handle exists
+        HIP_OK(hipStreamSynchronize(st));
+    } catch (...) {
+        (void)hipFree(m->d_depth);
+        throw;
+    }
+    *out = m.release();
+}
+
+void add_device_impl(speq_markers* m, const uint8_t* d_seq, const uint8_t* d_qual, const uint64_t* d_offsets,
+                     uint64_t n_reads, hipStream_t st) {
+    if (n_reads > 0 && (!d_seq || !d_qual || !d_offsets))
+        throw std::invalid_argument("speq_markers_add_reads_device: null buffer");
+    if (!m) throw std::invalid_argument("speq_markers_add_reads_device: null handle");
+    if (n_reads == 0) return;
+    speq_device_index* d = m->dev;
+    DeviceGuard g(d->device);
+    const uint32_t k = m->params.k;
+    const DevView v = speq::search_view(d, k);
+    const uint64_t blocks = std::min<uint64_t>((n_reads + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 16384u);
+    hipLaunchKernelGGL(k_marker_reads, dim3((uint32_t)blocks), dim3(BLOCK_THREADS),
+                       (size_t)WAVES_PER_BLOCK * marker_wave_bytes(k), st, v, d_seq, d_qual, d_offsets, n_reads, k,
+                       m->params.phred_cutoff, m->d_depth);
+    HIP_OK(hipGetLastError());
+}
+
+// Batches of whole reads: at most BATCH_RECORDS records and (a single longer read aside) BATCH_BYTES bases each.
+constexpr uint64_t BATCH_RECORDS = 1ull << 20, BATCH_BYTES = 256ull << 20;
+
+void add_host_impl(speq_markers* m, const uint8_t* seq, const uint8_t* qual, const uint64_t* offsets,
+                   uint64_t n_reads) {
+    const char* who = "speq_markers_add_reads";
+    // (the handle last: every check of the arrays is made before anything of the device is touched)
+    if (n_reads > 0) {
+        if (!offsets) throw std::invalid_argument(std::string(who) + ": null offsets");
+        for (uint64_t i = 0; i < n_reads; ++i)
+            if (offsets[i + 1] < offsets[i])
+                throw std::invalid_argument(std::string(who) + ": offsets must be non-decreasing");
+        if (offsets[n_reads] > offsets[0] && (!seq || !qual))
+            throw std::invalid_argument(std::string(who) + ": null read buffer");
+    }
+    if (!m) throw std::invalid_argument(std::string(who) + ": null handle");
+    if (n_reads == 0) return;
+    speq_device_index* d = m->dev;
+    DeviceGuard g(d->device);
+    // one host add at a time per process: the batches go through the replica's stream and wait for it
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    std::vector<uint64_t> rel;
+    for (uint64_t r0 = 0; r0 < n_reads;) {
+        uint64_t r1 = r0 + 1;
+        while (r1 < n_reads && r1 + 1 - r0 <= BATCH_RECORDS && offsets[r1 + 1] - offsets[r0] <= BATCH_BYTES) ++r1;
+        const uint64_t n = r1 - r0, bytes = offsets[r1] - offsets[r0];
+        rel.resize(n + 1);
+        for (uint64_t i = 0; i <= n; ++i) rel[i] = offsets[r0 + i] - offsets[r0];
+        DevBuf ds(bytes, who), dq(bytes, who), dof((n + 1) * 8, who);
+        if (bytes) {
+            HIP_OK(hipMemcpyAsync(ds.p, seq + offsets[r0], bytes, hipMemcpyHostToDevice, d->stream));
+            HIP_OK(hipMemcpyAsync(dq.p, qual + offsets[r0], bytes, hipMemcpyHostToDevice, d->stream));
+        }
+        HIP_OK(hipMemcpyAsync(dof.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, d->stream));
+        add_device_impl(m, static_cast<const uint8_t*>(ds.p), static_cast<const uint8_t*>(dq.p),
+                        static_cast<const uint64_t*>(dof.p), n, d->stream);
+        HIP_OK(hipStreamSynchronize(d->stream));  // (the staging buffers go with the batch; nothing is copied back)
+        r0 = r1;
+    }
+}
+
+void finalize_impl(speq_markers* m, speq_marker_cov* out) {
+    if (!m) throw std::invalid_argument("speq_markers_finalize: null handle");
+    if (!out) throw std::invalid_argument("speq_markers_finalize: null output");
+    speq_device_index* d = m->dev;
+    DeviceGuard g(d->device);
+    HIP_OK(hipDeviceSynchronize());  // the adds of every stream of the device have completed
+    const uint32_t G = m->G;
+    DevBuf cov((size_t)G * sizeof(speq_marker_cov), "speq_markers_finalize");
+    hipStream_t st = d->stream;
+    HIP_OK(hipMemsetAsync(cov.p, 0, (size_t)G * sizeof(speq_marker_cov), st));
+    const DevView v = speq::search_view(d, m->params.k);
+    auto* o = static_cast<unsigned long long*>(cov.p);
+    if (G <= LDS_TALLY_GROUPS)
+        hipLaunchKernelGGL(k_marker_fold<true>, dim3(std::min(grid_1d(m->n), 2048u)), dim3(256), tally_bytes(G), st, v,
+                           m->d_depth, o);
+    else
+        hipLaunchKernelGGL(k_marker_fold<false>, dim3(grid_1d(m->n)), dim3(256), 0, st, v, m->d_depth, o);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(out, cov.p, (size_t)G * sizeof(speq_marker_cov), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+}
+
+void list_impl(speq_markers* m, uint64_t* n_markers, uint32_t* lo, uint32_t* group, uint32_t* depth) {
+    if (!m) throw std::invalid_argument("speq_markers_list: null handle");
+    speq_device_index* d = m->dev;
+    DeviceGuard g(d->device);
+    HIP_OK(hipDeviceSynchronize());
+    const uint64_t n = m->n;
+    std::vector<uint32_t> w(n), grp;
+    HIP_OK(hipMemcpy(w.data(), m->d_depth, n * 4, hipMemcpyDeviceToHost));
+    if (group) {
+        DevBuf dg(n * 4, "speq_markers_list");
+        hipLaunchKernelGGL(k_marker_groups, dim3(grid_1d(n)), dim3(256), 0, d->stream,
+                           speq::search_view(d, m->params.k), m->d_depth, static_cast<uint32_t*>(dg.p));
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipStreamSynchronize(d->stream));
+        grp.resize(n);
+        HIP_OK(hipMemcpy(grp.data(), dg.p, n * 4, hipMemcpyDeviceToHost));
+    }
+    uint64_t c = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (!(w[i] & MARK)) continue;
+        if (lo) lo[c] = (uint32_t)i;
+        if (group) group[c] = grp[i];
+        if (depth) depth[c] = w[i] & ~MARK;
+        ++c;
+    }
+    if (n_markers) *n_markers = c;
+}
+
+}  // namespace
+
+static_assert(sizeof(speq_marker_cov) == 96, "speq_marker_cov is twelve u64 words");
+
+extern "C" {
+
+int speq_markers_create(speq_device_index* d, const speq_scan_params* params, speq_markers** out) {
+    return guarded_nomem([&] { create_impl(d, params, out); });
+}
+
+int speq_markers_add_reads_device(speq_markers* m, const uint8_t* d_seq, const uint8_t* d_qual,
+                                  const uint64_t* d_offsets, uint64_t n_reads, void* stream) {
+    return guarded_nomem([&] { add_device_impl(m, d_seq, d_qual, d_offsets, n_reads, static_cast<hipStream_t>(stream)); });
+}
+
+int speq_markers_add_reads(speq_markers* m, const uint8_t* seq, const uint8_t* qual, const uint64_t* offsets,
+                           uint64_t n_reads) {
+    return guarded_nomem([&] { add_host_impl(m, seq, qual, offsets, n_reads); });
+}
+
+int speq_markers_finalize(speq_markers* m, speq_marker_cov* out) {
+    return guarded_nomem([&] { finalize_impl(m, out); });
+}
+
+int speq_markers_list(speq_markers* m, uint64_t* n_markers, uint32_t* lo, uint32_t* group, uint32_t* depth) {
+    return guarded_nomem([&] { list_impl(m, n_markers, lo, group, depth); });
+}
+
+void speq_markers_free(speq_markers* m) {
+    if (!m) return;
+    if (m->d_depth) (void)hipFree(m->d_depth);
+    delete m;
+}
+
+}  // extern "C"
