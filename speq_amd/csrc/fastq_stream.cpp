@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "host_reads.hpp"
 #include "scan_internal.hpp"
 
 // speq_report_fastq's result: the distinct group sets in ascending order with their unit counts, and the totals
@@ -823,6 +824,11 @@ struct HostSink : Sink {
         std::lock_guard<std::mutex> lk(mu);
         free_ids.push_back(slot);
     }
+    struct Release {  // gives the slot back when submit() leaves, however it leaves
+        HostSink& sink;
+        int32_t slot;
+        ~Release() { sink.release(slot); }
+    };
 };
 
 // Order-independent digest of the parsed records (sum over records of a 64-bit hash of length, bases and
@@ -859,11 +865,7 @@ struct ReportSink final : HostSink {
     ReportSink(speq_device_index* dev, const speq_scan_params& p)
         : d(dev), params(p), W((uint32_t)SPEQ_SET_WORDS(speq::device_groups(dev))) {}
     void submit(const speq_slot& s, uint64_t records) override {
-        struct Release {
-            ReportSink& sink;
-            int32_t slot;
-            ~Release() { sink.release(slot); }
-        } rel{*this, s.slot};
+        Release rel{*this, s.slot};
         if (records == 0) return;
         const uint64_t n_units = params.paired ? records / 2 : records;
         std::vector<speq_read_report> rep(n_units);
@@ -894,11 +896,7 @@ struct MarkerSink final : HostSink {
     speq_markers* m;
     explicit MarkerSink(speq_markers* handle) : m(handle) {}
     void submit(const speq_slot& s, uint64_t records) override {
-        struct Release {
-            MarkerSink& sink;
-            int32_t slot;
-            ~Release() { sink.release(slot); }
-        } rel{*this, s.slot};
+        Release rel{*this, s.slot};
         if (records == 0) return;
         check_rc(speq_markers_add_reads(m, s.seq, s.qual, s.offsets, records));
     }
@@ -918,6 +916,14 @@ uint32_t stream_slots(uint32_t threads) {
 struct StreamTotals {
     uint64_t records = 0, bases = 0, batches = 0;
 };
+
+void fill_stats(speq_stream_stats* stats, const StreamTotals& tot, std::chrono::steady_clock::time_point t0) {
+    if (!stats) return;
+    stats->records = tot.records;
+    stats->bases = tot.bases;
+    stats->batches = tot.batches;
+    stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
 
 // Offset just past the k-th '\n' of [p, p + n) (k >= 1), or n when there are fewer.
 size_t skip_lines(const char* p, size_t n, uint64_t k) {
@@ -1433,12 +1439,7 @@ void scan_fastq_impl(speq_device_index* const* ds, speq_em* const* ems, uint32_t
         tot.bases += speq::pipeline_gpu_parsed_bases(pls[i]);
     }
     for (uint32_t i = 0; i < n_dev; ++i) speq::return_cached_pipeline(ds[i], guards[i].release());
-    if (stats) {
-        stats->records = tot.records;
-        stats->bases = tot.bases;
-        stats->batches = tot.batches;
-        stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
+    fill_stats(stats, tot, t0);
 }
 
 }  // namespace
@@ -1526,8 +1527,7 @@ extern "C" int speq_report_fastq(speq_device_index* d, const char* path1, const 
                                  speq_stream_stats* stats) {
     return speq::guarded([&] {
         if (!d || !path1 || !params || !out) throw std::invalid_argument("speq_report_fastq: null argument");
-        if (params->k < 1 || params->k > SPEQ_REPORT_MAX_K)
-            throw std::invalid_argument("speq_report_fastq: k must be in [1, 1024]");
+        speq::check_report_k("speq_report_fastq", params->k);
         const auto t0 = std::chrono::steady_clock::now();
         speq_scan_params p = *params;
         p.paired = path2 != nullptr;
@@ -1543,12 +1543,7 @@ extern "C" int speq_report_fastq(speq_device_index* d, const char* path1, const 
         res->passing = sink.passing;
         res->unique = sink.unique;
         res->shared = sink.shared;
-        if (stats) {
-            stats->records = tot.records;
-            stats->bases = tot.bases;
-            stats->batches = tot.batches;
-            stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        }
+        fill_stats(stats, tot, t0);
         *out = res.release();
     });
 }
@@ -1559,8 +1554,7 @@ extern "C" int speq_markers_fastq(speq_device_index* d, const char* path1, const
     const auto t0 = std::chrono::steady_clock::now();
     int rc = speq::guarded([&] {
         if (!params) throw std::invalid_argument("speq_markers_fastq: null params");
-        if (params->k < 1 || params->k > SPEQ_REPORT_MAX_K)
-            throw std::invalid_argument("speq_markers_fastq: k must be in [1, 1024]");
+        speq::check_report_k("speq_markers_fastq", params->k);
         if (!d || !path1 || !out) throw std::invalid_argument("speq_markers_fastq: null argument");
     });
     if (rc != SPEQ_OK) return rc;
@@ -1571,12 +1565,7 @@ extern "C" int speq_markers_fastq(speq_device_index* d, const char* path1, const
         MarkerSink sink(m);
         const StreamTotals tot = run_stream(path1, path2, threads, sink, false, false);
         check_rc(speq_markers_finalize(m, out));
-        if (stats) {
-            stats->records = tot.records;
-            stats->bases = tot.bases;
-            stats->batches = tot.batches;
-            stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        }
+        fill_stats(stats, tot, t0);
     });
     speq_markers_free(m);
     return rc;

@@ -26,6 +26,7 @@
 
 #include "capi_internal.hpp"
 #include "em.hpp"
+#include "host_reads.hpp"
 #include "scan_internal.hpp"
 
 namespace {
@@ -1016,9 +1017,7 @@ void scan_host_pipelined(speq_device_index* d, const uint8_t* seq, const uint8_t
     std::fill(counts, counts + SPEQ_COUNTS_LEN(G), 0ull);
     if (weights) std::fill(weights, weights + G, 0.0);
     if (n_reads == 0) return;
-    for (uint64_t i = 0; i < n_reads; ++i)
-        if (offsets[i + 1] < offsets[i]) throw std::invalid_argument("speq_scan_reads: offsets must be non-decreasing");
-    if (offsets[n_reads] > offsets[0] && (!seq || !qual)) throw std::invalid_argument("speq_scan_reads: null read buffer");
+    check_host_reads("speq_scan_reads", seq, qual, offsets, n_reads);
     // 16 MiB batches, four filler threads: 4-32 MiB x 4-8 fillers all land at 32-34 GB/s of host bytes on the box
     // (profiles/r01/ab_host_batches.txt); 4 MiB loses to per-batch overheads.
     auto env_u = [](const char* name, uint64_t dflt) {  // A/B knobs (scripts/host_path_probe.py)
@@ -1034,8 +1033,7 @@ void scan_host_pipelined(speq_device_index* d, const uint8_t* seq, const uint8_t
     std::vector<std::pair<uint64_t, uint64_t>> batches;
     uint64_t max_bytes = 1, max_recs = step;
     for (uint64_t r0 = 0; r0 < n_reads;) {
-        uint64_t r1 = r0 + step;
-        while (r1 < n_reads && r1 - r0 < BATCH_RECORDS && offsets[r1 + step] - offsets[r0] <= BATCH_BYTES) r1 += step;
+        const uint64_t r1 = next_batch(offsets, n_reads, r0, step, BATCH_RECORDS, BATCH_BYTES);
         batches.emplace_back(r0, r1);
         max_bytes = std::max(max_bytes, offsets[r1] - offsets[r0]);
         max_recs = std::max(max_recs, r1 - r0);

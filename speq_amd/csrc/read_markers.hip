@@ -9,14 +9,12 @@
 #include <algorithm>
 #include <cstdint>
 #include <memory>
-#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "capi_internal.hpp"
-#include "device_index.hpp"
-#include "scan_device.hpp"
+#include "window_pass.hpp"
 
 struct speq_markers {
     speq_device_index* dev = nullptr;
@@ -37,72 +35,19 @@ constexpr uint32_t COV_WORDS = sizeof(speq_marker_cov) / 8;  // u64 words of one
 constexpr uint32_t TALLY_U32 = 3u + SPEQ_MARKER_BINS;
 __host__ __device__ inline uint32_t tally_bytes(uint32_t G) { return G * (8u + 4u * TALLY_U32); }
 
-struct OutOfDeviceMemory : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-
-void dev_alloc(void** p, size_t bytes, const char* who) {
-    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        throw OutOfDeviceMemory(std::string(who) + ": out of device memory (" + std::to_string(bytes) + " bytes)");
-    }
-    if (e != hipSuccess) throw speq::DeviceError(std::string(who) + ": hipMalloc: " + hipGetErrorString(e));
-}
-
-// guarded() with the device allocations' failure as SPEQ_E_NOMEM
+// guarded() with the device allocations' failure as SPEQ_E_NOMEM (guarded() keeps its message as a DeviceError's)
 template <typename F>
 int guarded_nomem(F&& f) {
-    int nomem = 0;
-    std::string msg;
+    bool nomem = false;
     const int rc = speq::guarded([&] {
         try {
             f();
-        } catch (const OutOfDeviceMemory& e) {
-            nomem = 1;
-            msg = e.what();
+        } catch (const OutOfDeviceMemory&) {
+            nomem = true;
+            throw;
         }
     });
-    if (!nomem) return rc;
-    speq::set_last_error(msg);
-    return SPEQ_E_NOMEM;
-}
-
-// Per-wave LDS: u16 prefix counts of bad positions [64 + k] | symbol codes [64 + k - 1], rounded to 16 B (the
-// report's layout).
-__host__ __device__ inline uint32_t marker_wave_bytes(uint32_t k) { return (3u * (64u + k) + 15u) & ~15u; }
-
-// One tile of 64 window starts over `span` staged positions (span <= 64 + k - 1): at(p) gives position p's symbol
-// code (0..3, or 4 for anything that ends a window) and whether it is bad; the wave's region then holds each symbol
-// and the number of bad positions before it, so window j passes iff cnt[j + k] == cnt[j]. Lane j searches window j
-// (has: window j exists; then j + k <= span) and returns the search's result with the interval start in `lo`.
-template <class At>
-__device__ __forceinline__ int search_tile(const DevView& I, const Rsrc& R, unsigned char* sym, uint16_t* cnt,
-                                           uint32_t span, uint32_t k, bool has, uint32_t lane, uint32_t& lo, At&& at) {
-    const uint64_t below = (1ull << lane) - 1ull;
-    uint32_t bad_before = 0;
-    for (uint32_t c = 0; c < span; c += 64u) {
-        const uint32_t p = c + lane;
-        const bool valid = p < span;
-        uint32_t s = 4u;
-        bool bad = false;
-        if (valid) at(p, s, bad);
-        const uint64_t bal = __ballot(bad);
-        if (valid) {
-            sym[p] = (unsigned char)s;
-            cnt[p] = (uint16_t)(bad_before + (uint32_t)__popcll(bal & below));
-        }
-        bad_before += (uint32_t)__popcll(bal);
-    }
-    if (lane == 0) cnt[span] = (uint16_t)bad_before;
-    wave_sync();
-    int res = -1;
-    if (has && cnt[lane + k] == cnt[lane]) {
-        uint32_t hi;
-        res = search_lds(I, R, sym + lane, k, true, lo, hi);
-    }
-    wave_sync();  // the next tile restages this wave's region
-    return res;
+    return nomem ? SPEQ_E_NOMEM : rc;
 }
 
 // Read pass: one wave64 per read, tiles of 64 window starts. A window whose k-mer lies in one group adds 1 to the
@@ -114,9 +59,8 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_marker_reads(const DevView I,
                                                                 uint32_t* __restrict__ depth) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    unsigned char* base = lds + wave * marker_wave_bytes(k);
-    uint16_t* cnt = reinterpret_cast<uint16_t*>(base);
-    unsigned char* sym = base + 2u * (64u + k);
+    uint16_t* cnt = wave_cnt(lds, wave, k);
+    unsigned char* sym = wave_sym(lds, wave, k);
     const Rsrc R = make_rsrc(I);
     for (uint64_t r = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave; r < n_reads;
          r += (uint64_t)gridDim.x * WAVES_PER_BLOCK) {
@@ -127,12 +71,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_marker_reads(const DevView I,
             const uint32_t span = (uint32_t)min((uint64_t)(64u + k - 1u), len - tile);
             uint32_t lo = 0;
             const int res = search_tile(I, R, sym, cnt, span, k, tile + lane < nwin, lane, lo,
-                                        [&](uint32_t p, uint32_t& s, bool& bad) {
-                                            const uint64_t at = beg + tile + p;
-                                            s = ascii_sym(seq[at]);
-                                            const int32_t q = min(max((int32_t)qual[at] - 33, 0), 41);
-                                            bad = s == 4u || (uint32_t)q <= cutoff;
-                                        });
+                                        SPEQ_READ_TILE_AT(seq, qual, beg + tile, cutoff));
             if (res >= 0 && lo < I.n) atomicAdd(&depth[lo], 1u);
         }
     }
@@ -145,9 +84,8 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_marker_texts(const DevView I,
                                                                 uint32_t k, uint32_t* __restrict__ depth) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    unsigned char* base = lds + wave * marker_wave_bytes(k);
-    uint16_t* cnt = reinterpret_cast<uint16_t*>(base);
-    unsigned char* sym = base + 2u * (64u + k);
+    uint16_t* cnt = wave_cnt(lds, wave, k);
+    unsigned char* sym = wave_sym(lds, wave, k);
     const Rsrc R = make_rsrc(I);
     const uint64_t n = I.n;
     if (n < k) return;
@@ -234,18 +172,10 @@ __global__ __launch_bounds__(256) void k_marker_groups(const DevView I, const ui
         group[i] = (depth[i] & MARK) ? (uint32_t)classify(I, R, (uint32_t)i, (uint32_t)i + 1u) : 0xFFFFFFFFu;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    DevBuf(size_t bytes, const char* who) { dev_alloc(&p, bytes, who); }
-    ~DevBuf() { (void)hipFree(p); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-};
-
 void check_create(const speq_device_index* d, const speq_scan_params* p, speq_markers** out) {
     const char* who = "speq_markers_create";
     if (!p) throw std::invalid_argument(std::string(who) + ": null params");
-    if (p->k < 1 || p->k > SPEQ_REPORT_MAX_K) throw std::invalid_argument(std::string(who) + ": k must be in [1, 1024]");
+    speq::check_report_k(who, p->k);
     if (!d) throw std::invalid_argument(std::string(who) + ": null device index");
     if (!out) throw std::invalid_argument(std::string(who) + ": null output");
 }
@@ -269,7 +199,7 @@ void create_impl(speq_device_index* d, const speq_scan_params* p, speq_markers**
         if (tiles) {
             const uint64_t blocks = std::min<uint64_t>((tiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 16384u);
             hipLaunchKernelGGL(k_marker_texts, dim3((uint32_t)blocks), dim3(BLOCK_THREADS),
-                               (size_t)WAVES_PER_BLOCK * marker_wave_bytes(p->k), st, v, d->d_text, p->k, m->d_depth);
+                               (size_t)WAVES_PER_BLOCK * wave_bytes(p->k), st, v, d->d_text, p->k, m->d_depth);
             HIP_OK(hipGetLastError());
         }
         // the adds come on the callers' streams: the marks are complete before the handle exists
@@ -293,51 +223,26 @@ void add_device_impl(speq_markers* m, const uint8_t* d_seq, const uint8_t* d_qua
     const DevView v = speq::search_view(d, k);
     const uint64_t blocks = std::min<uint64_t>((n_reads + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 16384u);
     hipLaunchKernelGGL(k_marker_reads, dim3((uint32_t)blocks), dim3(BLOCK_THREADS),
-                       (size_t)WAVES_PER_BLOCK * marker_wave_bytes(k), st, v, d_seq, d_qual, d_offsets, n_reads, k,
+                       (size_t)WAVES_PER_BLOCK * wave_bytes(k), st, v, d_seq, d_qual, d_offsets, n_reads, k,
                        m->params.phred_cutoff, m->d_depth);
     HIP_OK(hipGetLastError());
 }
-
-// Batches of whole reads: at most BATCH_RECORDS records and (a single longer read aside) BATCH_BYTES bases each.
-constexpr uint64_t BATCH_RECORDS = 1ull << 20, BATCH_BYTES = 256ull << 20;
 
 void add_host_impl(speq_markers* m, const uint8_t* seq, const uint8_t* qual, const uint64_t* offsets,
                    uint64_t n_reads) {
     const char* who = "speq_markers_add_reads";
     // (the handle last: every check of the arrays is made before anything of the device is touched)
-    if (n_reads > 0) {
-        if (!offsets) throw std::invalid_argument(std::string(who) + ": null offsets");
-        for (uint64_t i = 0; i < n_reads; ++i)
-            if (offsets[i + 1] < offsets[i])
-                throw std::invalid_argument(std::string(who) + ": offsets must be non-decreasing");
-        if (offsets[n_reads] > offsets[0] && (!seq || !qual))
-            throw std::invalid_argument(std::string(who) + ": null read buffer");
-    }
+    if (n_reads > 0 && !offsets) throw std::invalid_argument(std::string(who) + ": null offsets");
+    speq::check_host_reads(who, seq, qual, offsets, n_reads);
     if (!m) throw std::invalid_argument(std::string(who) + ": null handle");
     if (n_reads == 0) return;
     speq_device_index* d = m->dev;
     DeviceGuard g(d->device);
-    // one host add at a time per process: the batches go through the replica's stream and wait for it
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    std::vector<uint64_t> rel;
-    for (uint64_t r0 = 0; r0 < n_reads;) {
-        uint64_t r1 = r0 + 1;
-        while (r1 < n_reads && r1 + 1 - r0 <= BATCH_RECORDS && offsets[r1 + 1] - offsets[r0] <= BATCH_BYTES) ++r1;
-        const uint64_t n = r1 - r0, bytes = offsets[r1] - offsets[r0];
-        rel.resize(n + 1);
-        for (uint64_t i = 0; i <= n; ++i) rel[i] = offsets[r0 + i] - offsets[r0];
-        DevBuf ds(bytes, who), dq(bytes, who), dof((n + 1) * 8, who);
-        if (bytes) {
-            HIP_OK(hipMemcpyAsync(ds.p, seq + offsets[r0], bytes, hipMemcpyHostToDevice, d->stream));
-            HIP_OK(hipMemcpyAsync(dq.p, qual + offsets[r0], bytes, hipMemcpyHostToDevice, d->stream));
-        }
-        HIP_OK(hipMemcpyAsync(dof.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, d->stream));
-        add_device_impl(m, static_cast<const uint8_t*>(ds.p), static_cast<const uint8_t*>(dq.p),
-                        static_cast<const uint64_t*>(dof.p), n, d->stream);
-        HIP_OK(hipStreamSynchronize(d->stream));  // (the staging buffers go with the batch; nothing is copied back)
-        r0 = r1;
-    }
+    // (the staging buffers go with the batch; nothing is copied back)
+    for_staged_batches(who, d, seq, qual, offsets, n_reads, 1,
+                       [&](const uint8_t* d_seq, const uint8_t* d_qual, const uint64_t* d_off, uint64_t, uint64_t n) {
+                           add_device_impl(m, d_seq, d_qual, d_off, n, d->stream);
+                       });
 }
 
 void finalize_impl(speq_markers* m, speq_marker_cov* out) {

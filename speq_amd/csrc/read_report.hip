@@ -6,14 +6,11 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
 #include <stdexcept>
 #include <string>
-#include <vector>
 
 #include "capi_internal.hpp"
-#include "device_index.hpp"
-#include "scan_device.hpp"
+#include "window_pass.hpp"
 
 namespace {
 
@@ -21,14 +18,10 @@ using namespace speq_dev;
 
 constexpr uint32_t NO_GROUP = 0xFFFFFFFFu;
 
-// Per-wave LDS: u16 prefix counts of bad positions [64 + k] | symbol codes [64 + k - 1], rounded to 16 B.
-__host__ __device__ inline uint32_t report_wave_bytes(uint32_t k) { return (3u * (64u + k) + 15u) & ~15u; }
-
-// One wave64 owns one unit (a read, or the pair 2u, 2u + 1) and walks each mate in tiles of 64 window starts. A tile
-// stages the 64 + k - 1 positions under its windows: the symbol code of each and the number of bad positions (N, or
-// quality <= cutoff) before it, so window j passes iff cnt[j + k] == cnt[j] (two LDS loads). Lane j then searches
-// window tile + j; ballots fold the lanes' results into the unit's record and group set. No other wave touches the
-// unit's rows, so lane 0 writes them with plain loads and stores (the launcher cleared the set rows).
+// One wave64 owns one unit (a read, or the pair 2u, 2u + 1) and walks each mate in tiles of 64 window starts; lane j
+// searches window tile + j (search_tile, window_pass.hpp) and ballots fold the lanes' results into the unit's record
+// and group set. No other wave touches the unit's rows, so lane 0 writes them with plain loads and stores (the
+// launcher cleared the set rows).
 template <bool PAIRED>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_read_report(const DevView I, const uint8_t* __restrict__ seq,
                                                                const uint8_t* __restrict__ qual,
@@ -38,11 +31,9 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_read_report(const DevView I, 
                                                                uint64_t* __restrict__ sets) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    unsigned char* base = lds + wave * report_wave_bytes(k);
-    uint16_t* cnt = reinterpret_cast<uint16_t*>(base);
-    unsigned char* sym = base + 2u * (64u + k);
+    uint16_t* cnt = wave_cnt(lds, wave, k);
+    unsigned char* sym = wave_sym(lds, wave, k);
     const Rsrc R = make_rsrc(I);
-    const uint64_t below = (1ull << lane) - 1ull;
     for (uint64_t u = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave; u < n_units;
          u += (uint64_t)gridDim.x * WAVES_PER_BLOCK) {
         uint32_t passing = 0, unique = 0, shared = 0, first = NO_GROUP;
@@ -54,34 +45,10 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_read_report(const DevView I, 
             const uint64_t nwin = len - k + 1u;
             for (uint64_t tile = 0; tile < nwin; tile += 64u) {
                 const uint32_t span = (uint32_t)min((uint64_t)(64u + k - 1u), len - tile);  // staged positions
-                uint32_t bad_before = 0;
-                for (uint32_t c = 0; c < span; c += 64u) {
-                    const uint32_t p = c + lane;
-                    const bool valid = p < span;
-                    uint32_t s = 4u;
-                    bool bad = false;
-                    if (valid) {
-                        const uint64_t at = beg + tile + p;
-                        s = ascii_sym(seq[at]);
-                        const int32_t q = min(max((int32_t)qual[at] - 33, 0), 41);
-                        bad = s == 4u || (uint32_t)q <= cutoff;
-                    }
-                    const uint64_t bal = __ballot(bad);
-                    if (valid) {
-                        sym[p] = (unsigned char)s;
-                        cnt[p] = (uint16_t)(bad_before + (uint32_t)__popcll(bal & below));
-                    }
-                    bad_before += (uint32_t)__popcll(bal);
-                }
-                if (lane == 0) cnt[span] = (uint16_t)bad_before;
-                wave_sync();
-                const bool has = tile + lane < nwin;  // then lane + k <= span
-                const bool pass = has && cnt[lane + k] == cnt[lane];
-                int res = -1;
-                if (pass) {
-                    uint32_t lo, hi;
-                    res = search_lds(I, R, sym + lane, k, true, lo, hi);
-                }
+                uint32_t lo = 0;
+                bool pass;
+                const int res = search_tile(I, R, sym, cnt, span, k, tile + lane < nwin, lane, lo,
+                                            SPEQ_READ_TILE_AT(seq, qual, beg + tile, cutoff), &pass);
                 const uint64_t b_uni = __ballot(res >= 0);
                 passing += (uint32_t)__popcll(__ballot(pass));
                 unique += (uint32_t)__popcll(b_uni);
@@ -95,7 +62,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_read_report(const DevView I, 
                         if (lane == 0 && (uint32_t)g < I.G) row[(uint32_t)g >> 6] |= 1ull << ((uint32_t)g & 63u);
                     }
                 }
-                wave_sync();  // the next tile restages this wave's region
             }
         }
         if (lane == 0) reports[u] = make_uint4(passing, unique, shared, first);
@@ -104,8 +70,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_read_report(const DevView I, 
 
 void check_params(const char* who, const speq_device_index* d, const speq_scan_params* p, uint64_t n_reads) {
     if (!p) throw std::invalid_argument(std::string(who) + ": null params");
-    if (p->k < 1 || p->k > SPEQ_REPORT_MAX_K)
-        throw std::invalid_argument(std::string(who) + ": k must be in [1, 1024]");
+    speq::check_report_k(who, p->k);
     if (p->paired && (n_reads & 1))
         throw std::invalid_argument(std::string(who) + ": paired report needs an even record count");
     if (!d) throw std::invalid_argument(std::string(who) + ": null device index");
@@ -125,65 +90,35 @@ void report_device_impl(speq_device_index* d, const uint8_t* d_seq, const uint8_
     const uint32_t W = (uint32_t)SPEQ_SET_WORDS(d->G);
     HIP_OK(hipMemsetAsync(d_sets, 0, n_units * W * sizeof(uint64_t), st));
     const DevView v = speq::search_view(d, p->k);
-    const size_t lds = (size_t)WAVES_PER_BLOCK * report_wave_bytes(p->k);  // 13 KiB at k = 1024
+    const size_t lds = (size_t)WAVES_PER_BLOCK * wave_bytes(p->k);  // 13 KiB at k = 1024
     const uint64_t blocks = std::min<uint64_t>((n_units + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 16384u);
     uint4* rep = reinterpret_cast<uint4*>(d_reports);
-    if (p->paired)
-        hipLaunchKernelGGL(k_read_report<true>, dim3((uint32_t)blocks), dim3(BLOCK_THREADS), lds, st, v, d_seq, d_qual,
-                           d_offsets, n_units, p->k, p->phred_cutoff, W, rep, d_sets);
-    else
-        hipLaunchKernelGGL(k_read_report<false>, dim3((uint32_t)blocks), dim3(BLOCK_THREADS), lds, st, v, d_seq, d_qual,
-                           d_offsets, n_units, p->k, p->phred_cutoff, W, rep, d_sets);
+    const auto kernel = p->paired ? k_read_report<true> : k_read_report<false>;
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(BLOCK_THREADS), lds, st, v, d_seq, d_qual, d_offsets, n_units,
+                       p->k, p->phred_cutoff, W, rep, d_sets);
     HIP_OK(hipGetLastError());
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    explicit DevBuf(size_t bytes) { HIP_OK(hipMalloc(&p, std::max<size_t>(bytes, 16))); }
-    ~DevBuf() { (void)hipFree(p); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-};
-
-// Batches of whole units: at most BATCH_RECORDS records and (a single longer unit aside) BATCH_BYTES bases each.
-constexpr uint64_t BATCH_RECORDS = 1ull << 20, BATCH_BYTES = 256ull << 20;
-
 void report_host_impl(speq_device_index* d, const uint8_t* seq, const uint8_t* qual, const uint64_t* offsets,
                       uint64_t n_reads, const speq_scan_params* p, speq_read_report* reports, uint64_t* sets) {
-    check_params("speq_report_reads", d, p, n_reads);
+    const char* who = "speq_report_reads";
+    check_params(who, d, p, n_reads);
     if (n_reads == 0) return;
     if (!offsets || !reports || !sets) throw std::invalid_argument("speq_report_reads: null argument");
-    for (uint64_t i = 0; i < n_reads; ++i)
-        if (offsets[i + 1] < offsets[i]) throw std::invalid_argument("speq_report_reads: offsets must be non-decreasing");
-    if (offsets[n_reads] > offsets[0] && (!seq || !qual)) throw std::invalid_argument("speq_report_reads: null read buffer");
-    const uint32_t per = p->paired ? 2u : 1u;
-    const uint32_t W = (uint32_t)SPEQ_SET_WORDS(d->G);
+    speq::check_host_reads(who, seq, qual, offsets, n_reads);
+    const uint32_t per = p->paired ? 2u : 1u, W = (uint32_t)SPEQ_SET_WORDS(d->G);
     DeviceGuard g(d->device);
-    // one report at a time per process: the batches go through the replica's stream and wait for it
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    std::vector<uint64_t> rel;
-    for (uint64_t r0 = 0; r0 < n_reads;) {
-        uint64_t r1 = r0 + per;
-        while (r1 < n_reads && r1 + per - r0 <= BATCH_RECORDS && offsets[r1 + per] - offsets[r0] <= BATCH_BYTES) r1 += per;
-        const uint64_t n = r1 - r0, units = n / per, bytes = offsets[r1] - offsets[r0];
-        rel.resize(n + 1);
-        for (uint64_t i = 0; i <= n; ++i) rel[i] = offsets[r0 + i] - offsets[r0];
-        DevBuf ds(bytes), dq(bytes), dof((n + 1) * 8), drep(units * sizeof(speq_read_report)), dset(units * W * 8);
-        if (bytes) {
-            HIP_OK(hipMemcpyAsync(ds.p, seq + offsets[r0], bytes, hipMemcpyHostToDevice, d->stream));
-            HIP_OK(hipMemcpyAsync(dq.p, qual + offsets[r0], bytes, hipMemcpyHostToDevice, d->stream));
-        }
-        HIP_OK(hipMemcpyAsync(dof.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, d->stream));
-        report_device_impl(d, static_cast<const uint8_t*>(ds.p), static_cast<const uint8_t*>(dq.p),
-                           static_cast<const uint64_t*>(dof.p), n, p, static_cast<speq_read_report*>(drep.p),
+    const uint64_t most = std::min(n_reads, BATCH_RECORDS) / per;  // units of the largest batch
+    DevBuf drep(most * sizeof(speq_read_report), who), dset(most * W * 8, who);
+    const StagedPass pass = [&](const uint8_t* d_seq, const uint8_t* d_qual, const uint64_t* d_off, uint64_t r0,
+                                uint64_t n) {  // (the results leave with the batch's one stream wait)
+        const uint64_t units = n / per, u0 = r0 / per;
+        report_device_impl(d, d_seq, d_qual, d_off, n, p, static_cast<speq_read_report*>(drep.p),
                            static_cast<uint64_t*>(dset.p), d->stream);
-        const uint64_t u0 = r0 / per;
         HIP_OK(hipMemcpyAsync(reports + u0, drep.p, units * sizeof(speq_read_report), hipMemcpyDeviceToHost, d->stream));
         HIP_OK(hipMemcpyAsync(sets + u0 * W, dset.p, units * W * 8, hipMemcpyDeviceToHost, d->stream));
-        HIP_OK(hipStreamSynchronize(d->stream));
-        r0 = r1;
-    }
+    };
+    for_staged_batches(who, d, seq, qual, offsets, n_reads, per, pass);
 }
 
 }  // namespace

@@ -115,6 +115,16 @@ def base_reads(k: int, paired: bool = False):
     return pack(*base_read_list(k))
 
 
+def tiled(seq: bytes, qual: bytes, off: np.ndarray, n: int):
+    """(seq, qual, offsets) of n records: the read set repeated end to end, the last repeat cut after a record."""
+    n0 = len(off) - 1
+    i = np.arange(n + 1, dtype=np.int64)
+    off_t = ((i // n0) * int(off[n0]) + off[i % n0].astype(np.int64)).astype(np.uint64)
+    nb = int(off_t[n])
+    return (np.resize(np.frombuffer(seq, np.uint8), nb).tobytes(), np.resize(np.frombuffer(qual, np.uint8), nb).tobytes(),
+            off_t)
+
+
 # ---- more than 64 groups: 70 groups of one random 300-bp record ----
 MANY_K = 21
 

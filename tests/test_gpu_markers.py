@@ -254,6 +254,31 @@ def _to_device(reads):
             torch.from_numpy(np.asarray(off).astype(np.int64)).cuda())
 
 
+def test_host_add_across_a_batch_edge():
+    """speq_markers_add_reads stages at most 2^20 records per batch: 2^20 + 3 reads of the base read set repeated end
+    to end. The expected depths are the model's over the whole set times the whole repeats, plus the model's over the
+    reads of the cut last repeat; the markers themselves do not change."""
+    from collections import Counter
+    k = 21
+    n = (1 << 20) + 3
+    reads = ri.base_reads(k)
+    reps, rem = divmod(n, len(reads[2]) - 1)
+    assert rem
+    whole = base_model(k)
+    ref = ri.base_ref()
+    part = mm.coverage(er.build_index(ref.records, ref.groups, 3, k), 3, k, *_split(reads, 0, rem), ri.CUTOFF)
+    exp = mm.Coverage(3, whole.group_of, Counter({w: reps * d for w, d in whole.depth.items()}) + part.depth)
+    assert sum(exp.hits) == reps * sum(whole.hits) + sum(part.hits) and 0 < sum(part.hits) < sum(whole.hits)
+    idx = base_index()
+    dev = DeviceIndex(idx)
+    m = Markers(dev, k, ri.CUTOFF)
+    m.add(*ri.tiled(*reads, n))
+    cov = assert_equal(m, idx, k, exp)
+    assert cov.markers.tolist() == whole.markers
+    m.close()
+    dev.close()
+
+
 def test_accumulation():
     import torch
     k = 21

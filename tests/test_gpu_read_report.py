@@ -104,6 +104,27 @@ def test_report_equals_the_model_and_the_scan_counters(k, paired):
     dev.close()
 
 
+@pytest.mark.parametrize("paired", [False, True], ids=["single", "paired"])
+def test_host_report_across_a_batch_edge(paired):
+    """speq_report_reads stages at most 2^20 records per batch: 2^20 + 3 reads, or 2^20 + 4 as pairs (one pair starts
+    exactly at the cut), of the base read set repeated end to end give the model's records and sets repeated the same
+    way. The count is no multiple of the set's size, so a record sits at another place in every repeat."""
+    k = 21
+    n = (1 << 20) + (4 if paired else 3)
+    seq, qual, off = ri.base_reads(k)
+    n0 = len(off) - 1
+    assert n0 % 2 == 0 and n % n0 != 0
+    exp = base_model(k, paired)
+    n_units = n // 2 if paired else n
+    dev = DeviceIndex(base_index())
+    got = dev.report(*ri.tiled(seq, qual, off, n), k=k, phred_cutoff=ri.CUTOFF, paired=paired)
+    for name in ("passing", "unique", "shared", "first_group"):
+        np.testing.assert_array_equal(getattr(got, name), np.resize(np.array(getattr(exp, name), np.int64), n_units),
+                                      err_msg=name)
+    np.testing.assert_array_equal(got.sets, np.resize(exp.words(), (n_units, exp.W)))
+    dev.close()
+
+
 def test_odd_paired_count_is_refused():
     from speq_amd import SpeqError
     dev = DeviceIndex(base_index())
