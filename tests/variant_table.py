@@ -75,6 +75,11 @@ class RefShape(NamedTuple):
 
 REFS = {"g5": RefShape(5, 2, 3000, 0.001),      # the LDS plane
         "g2049": RefShape(2049, 1, 220, 0.0)}   # the smallest G past LDS_HIST_MAX_G: global atomics
+# The replicas of tests/test_gpu_big_k.py (k past the anchor kernel and every table): `predict` takes recipes on them,
+# the plan and ALL_VARIANTS do not. Only G enters the rules at those k (their texts are not of this shape: three
+# records of tests/big_k_inputs.py under labels up to G - 1).
+BIG_K_REFS = {"big3": RefShape(3, 1, 12000, 0.0), "big2048": RefShape(2048, 1, 12000, 0.0),
+              "big2049": RefShape(2049, 1, 12000, 0.0)}
 
 
 # ---------------------------------------------------------------- recipes
@@ -116,7 +121,8 @@ def read_len(k: int) -> int:
 
 
 def predict(r: Recipe) -> Variant:
-    shape = REFS[r.ref]
+    shape = REFS[r.ref] if r.ref in REFS else BIG_K_REFS[r.ref]
+    assert r.ref in REFS or r.k > 128, "the shapes of BIG_K_REFS state G alone"
     t = dict(DEFAULTS)
     t.update(dict(r.tune))
     k = r.k
