@@ -233,6 +233,55 @@ int speq_markers_finalize(speq_markers* m, speq_marker_cov* out);
 int speq_markers_list(speq_markers* m, uint64_t* n_markers, uint32_t* lo, uint32_t* group, uint32_t* depth);
 void speq_markers_free(speq_markers* m);
 
+/* ---- read bootstrap: how far to trust a percentage (a diagnostic pass beside the scan) ----
+ * The scan's counter vector under B Poisson(1) resamplings of the reads, in one pass. The resampling unit is the read,
+ * or the pair (2i, 2i + 1) when params->paired is set: windows of one read are strongly correlated. Unit u, replicate
+ * b = 1 .. B has the integer weight
+ *   w = #{j in 0 .. 20 : h >= C_j},  h = mix(x + g b),  x = mix(seed + g (u + 1)),  g = 0x9e3779b97f4a7c15,
+ *   mix = splitmix64's finaliser,  C_j = floor(2^64 e^-1 sum_{i <= j} 1 / i!)   (all mod 2^64; w <= 21),
+ * and replicate 0 is the sample itself (every weight 1). u is the unit's position in the input, always passed
+ * explicitly (first_unit + its position in the call): no handle keeps a running count, so the result depends on no
+ * batch cut, block order, thread count or grid size. Per unit: P passing windows, c[g] windows unique to group g, amb =
+ * 1 iff two or more c[g] are non-zero. counts is u64 [B + 1][G + 2], row b a counter vector in SPEQ_COUNTS_LEN layout:
+ * [b][0] = sum_u w P_u, [b][1] = sum_u w amb_u, [b][2 + g] = sum_u w c_u[g]; row 0 equals a scan of the same reads.
+ * With params->mode == SPEQ_MODE_LOCAL there is also weights, f64 [B + 1][G]: [b][g] = sum_u w (sum of the scan's Phred
+ * weight over u's windows unique to g). Window filter and base conversion are the scan's. Every passing window is
+ * searched exactly (no per-k structure), as in the per-unit report: an opt-in pass, not the hot path. The replica must
+ * outlive the handle. The reference keeps none of this. */
+#define SPEQ_BOOTSTRAP_MAX_REPLICATES 1024
+typedef struct speq_bootstrap speq_bootstrap;
+/* Fixes params (k in 1 .. SPEQ_REPORT_MAX_K, phred_cutoff, paired, mode), 1 .. SPEQ_BOOTSTRAP_MAX_REPLICATES replicates
+ * and the seed; the accumulators live on the replica's GPU (blocking). */
+int speq_bootstrap_create(speq_device_index* d, const speq_scan_params* params, uint32_t replicates, uint64_t seed,
+                          speq_bootstrap** out);
+/* Adds n_reads records (an even number for a paired handle) whose first unit has index first_unit. Device buffers,
+ * asynchronous on stream; writes nothing but the handle's accumulators. n_reads == 0 launches nothing. */
+int speq_bootstrap_add_reads_device(speq_bootstrap* b, const uint8_t* d_seq, const uint8_t* d_qual,
+                                    const uint64_t* d_offsets, uint64_t n_reads, uint64_t first_unit, void* stream);
+/* Host buffers, synchronous, staged in batches like speq_report_reads; first_unit counts units, not records. */
+int speq_bootstrap_add_reads(speq_bootstrap* b, const uint8_t* seq, const uint8_t* qual, const uint64_t* offsets,
+                             uint64_t n_reads, uint64_t first_unit);
+/* Waits for the adds of every stream of the device; counts[(B + 1)(G + 2)] and, for a local handle, weights[(B + 1) G]
+ * (NULL otherwise) are overwritten with the totals so far. The handle stays usable, like speq_markers_finalize. */
+int speq_bootstrap_finalize(speq_bootstrap* b, uint64_t* counts, double* weights);
+/* Any output may be NULL. *lds_path: 1 when the last add accumulated per block in LDS, 0 when it used device atomics
+ * throughout (the accumulators did not fit); *units_added: units of every add so far. */
+int speq_bootstrap_info(const speq_bootstrap* b, uint32_t* replicates, uint32_t* lds_path, uint64_t* units_added);
+void speq_bootstrap_free(speq_bootstrap* b);
+/* Host test accessor: the weight of (seed, unit, replicate) as the kernel computes it. */
+uint32_t speq_bootstrap_weight(uint64_t seed, uint64_t unit, uint32_t replicate);
+/* Host only: per group, the percentage of the sample and its spread over the replicates. Row b's percentage of group
+ * g is unique_to_percent of that row: 100 ur / counts[b][0] / (u_ref[g] / tot_ref[g]) with ur = weights[b][g] when
+ * weights is given, else counts[b][2 + g] * unique_scale (the CLI passes 1 / fixed_accuracy^k); 0 where tot_ref[g] ==
+ * 0. estimate is row 0's. Replicates with counts[b][0] == 0 are left out; `used` counts the rest, n. Over their values
+ * v in replicate order: mean = sum v / n, se = sqrt(sum (v - mean)^2 / (n - 1)) (0 when n < 2), plain sequential f64
+ * sums; sorted ascending with t = floor(n (1 - level) / 2): lo = v[t], hi = v[n - 1 - t]. 0 < level < 1. n = 0:
+ * everything but estimate is 0. */
+typedef struct { double estimate, mean, se, lo, hi; uint64_t used; } speq_bootstrap_ci; /* 48 bytes */
+int speq_bootstrap_summary(const uint64_t* counts, const double* weights, uint32_t replicates, uint32_t n_groups,
+                           const uint64_t* u_ref, const uint64_t* tot_ref, double unique_scale, double level,
+                           speq_bootstrap_ci* out /* [G] */);
+
 /* ---- reference-uniqueness pass (replaces _async_count_unique_kmers_per_group, fm_scanner.cpp:1476-1576)
  * For every window of every text (fwd and rc of each record): Tot_ref[g] += 1, and U_ref[g] += 1 iff
  * every occurrence lies in a text of group g.  Outputs are host arrays of G u64 (overwritten). */
@@ -367,6 +416,14 @@ void speq_group_sets_free(speq_group_sets* s);
  * blocks parsed on host threads and added in any order, one finalize at the end into out[G]. stats may be NULL. */
 int speq_markers_fastq(speq_device_index* d, const char* path1, const char* path2, const speq_scan_params* params,
                        uint32_t threads, speq_marker_cov* out, speq_stream_stats* stats);
+
+/* The read bootstrap (speq_bootstrap_*) of the whole of FASTQ file(s) (plain or gzip; paired when path2 != NULL)
+ * through a handle of its own: blocks parsed on host threads and added in any order, each with the index of its first
+ * record in the file, so the result equals speq_bootstrap_add_reads of the same records with first_unit = 0 for any
+ * `threads`. weights is NULL unless params->mode is local; stats may be NULL. */
+int speq_bootstrap_fastq(speq_device_index* d, const char* path1, const char* path2, const speq_scan_params* params,
+                         uint32_t replicates, uint64_t seed, uint32_t threads, uint64_t* counts, double* weights,
+                         speq_stream_stats* stats);
 
 /* ---- several GPUs in one process ----
  * Reads shard across the GPUs of a node, the index is replicated (one speq_device_index per GPU, opened from the

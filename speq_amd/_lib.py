@@ -62,6 +62,14 @@ class MarkerCov(C.Structure):
                 ("depth_hist", C.c_uint64 * MARKER_BINS)]
 
 
+BOOTSTRAP_MAX_REPLICATES = 1024
+
+
+class BootstrapCI(C.Structure):
+    _fields_ = [("estimate", C.c_double), ("mean", C.c_double), ("se", C.c_double), ("lo", C.c_double),
+                ("hi", C.c_double), ("used", C.c_uint64)]
+
+
 _U32P = C.POINTER(C.c_uint32)
 SIGNATURES = {
     "speq_last_error": (C.c_char_p, []),
@@ -100,6 +108,17 @@ SIGNATURES = {
     "speq_markers_fastq": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.POINTER(ScanParams), C.c_uint32, _P,
                                      C.POINTER(StreamStats)]),
     "speq_markers_free": (None, [_P]),
+    "speq_bootstrap_create": (C.c_int, [_P, C.POINTER(ScanParams), C.c_uint32, C.c_uint64, C.POINTER(_P)]),
+    "speq_bootstrap_add_reads_device": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_uint64, _P]),
+    "speq_bootstrap_add_reads": (C.c_int, [_P, C.c_char_p, C.c_char_p, _U64P, C.c_uint64, C.c_uint64]),
+    "speq_bootstrap_finalize": (C.c_int, [_P, _U64P, _F64P]),
+    "speq_bootstrap_info": (C.c_int, [_P, _U32P, _U32P, _U64P]),
+    "speq_bootstrap_free": (None, [_P]),
+    "speq_bootstrap_fastq": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.POINTER(ScanParams), C.c_uint32, C.c_uint64,
+                                       C.c_uint32, _U64P, _F64P, C.POINTER(StreamStats)]),
+    "speq_bootstrap_weight": (C.c_uint32, [C.c_uint64, C.c_uint64, C.c_uint32]),
+    "speq_bootstrap_summary": (C.c_int, [_U64P, _F64P, C.c_uint32, C.c_uint32, _U64P, _U64P, C.c_double, C.c_double,
+                                         C.POINTER(BootstrapCI)]),
     "speq_ref_unique": (C.c_int, [_P, C.c_uint32, _U64P, _U64P]),
     "speq_ref_unique_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P]),
     "speq_comm_unique_id": (C.c_int, [_P]),

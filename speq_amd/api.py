@@ -20,10 +20,10 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import (MARKER_BINS, SPEQ_MODE_GLOBAL, SPEQ_MODE_LOCAL, BuildOpts, IndexInfo, ScanParams, Slot,  # noqa: F401
-                   SpeqError, StreamStats, check, lib)
+from ._lib import (MARKER_BINS, SPEQ_MODE_GLOBAL, SPEQ_MODE_LOCAL, BootstrapCI, BuildOpts, IndexInfo,  # noqa: F401
+                   ScanParams, Slot, SpeqError, StreamStats, check, lib)
 
-__all__ = ["FmIndex", "DeviceIndex", "Node", "Pipeline", "ScanResult", "ReadReport", "Markers", "MarkerCoverage", "Groupings", "EmHistogram", "Comm", "file_to_map", "unique_to_percent",
+__all__ = ["FmIndex", "DeviceIndex", "Node", "Pipeline", "ScanResult", "ReadReport", "Markers", "MarkerCoverage", "Bootstrap", "bootstrap_summary", "Groupings", "EmHistogram", "Comm", "file_to_map", "unique_to_percent",
            "em_refine", "pack_records", "SpeqError", "SPEQ_MODE_GLOBAL", "SPEQ_MODE_LOCAL"]
 
 
@@ -328,6 +328,31 @@ class DeviceIndex:
                                        rec.ctypes.data, None))
         return MarkerCoverage.from_records(rec)
 
+    def bootstrap(self, seq: bytes, qual: bytes, offsets: np.ndarray, k: int, replicates: int = 200, seed: int = 1,
+                  phred_cutoff: int = 30, paired: bool = False, local: bool = False, first_unit: int = 0):
+        """The read bootstrap of host reads (speq_bootstrap_*): one handle, one add, one finalize. Returns (counts
+        [B + 1, G + 2] u64, weights [B + 1, G] f64 or None); row 0 is the scan's own result. A diagnostic pass, far
+        slower than scan()."""
+        b = Bootstrap(self, k, replicates, seed, phred_cutoff, paired, local)
+        try:
+            b.add(seq, qual, offsets, first_unit)
+            return b.finalize()
+        finally:
+            b.close()
+
+    def bootstrap_fastq(self, path1: str, path2: Optional[str] = None, k: int = 21, replicates: int = 200,
+                        seed: int = 1, phred_cutoff: int = 30, local: bool = False, threads: int = 4):
+        """The read bootstrap of FASTQ(.gz) file(s) (speq_bootstrap_fastq; paired when path2 is given): the same
+        (counts, weights) as bootstrap() of the files' records in file order, for any `threads`."""
+        G = self.n_groups
+        counts = np.zeros((replicates + 1, G + 2), dtype=np.uint64)
+        w = np.zeros((replicates + 1, G), dtype=np.float64) if local else None
+        p = ScanParams(k, phred_cutoff, int(path2 is not None), SPEQ_MODE_LOCAL if local else SPEQ_MODE_GLOBAL)
+        check(lib().speq_bootstrap_fastq(self._h, path1.encode(), path2.encode() if path2 else None, C.byref(p),
+                                         replicates, seed, threads, _u64p(counts),
+                                         w.ctypes.data_as(C.POINTER(C.c_double)) if w is not None else None, None))
+        return counts, w
+
     AX_STATS_KEYS = ("wave_iters", "lookup_lanes", "run_lanes", "lookup_waves", "run_waves", "run_windows",
                      "deferred", "filter_pass", "p2_probes", "p2_verify", "chunks", "segments", "qual_bytes",
                      "run_tallied", "run_granules", "refills", "busy_1_4", "busy_5_16", "busy_17_32", "busy_33_64",
@@ -487,6 +512,74 @@ class Markers:
             self.close()
         except Exception:
             pass
+
+
+class Bootstrap:
+    """B Poisson(1) resamplings of the reads' units in one pass (speq_bootstrap_*): add / add_device accumulate B + 1
+    counter vectors on the GPU, each call with the index of its first unit in the input; finalize returns them and
+    may be called again after more adds."""
+
+    def __init__(self, dev: DeviceIndex, k: int, replicates: int = 200, seed: int = 1, phred_cutoff: int = 30,
+                 paired: bool = False, local: bool = False):
+        self.dev = dev
+        self.n_groups = dev.n_groups
+        self.replicates = replicates
+        self.local = local
+        p = ScanParams(k, phred_cutoff, int(paired), SPEQ_MODE_LOCAL if local else SPEQ_MODE_GLOBAL)
+        h = C.c_void_p()
+        check(lib().speq_bootstrap_create(dev.handle, C.byref(p), replicates, seed, C.byref(h)))
+        self._h = h
+
+    def add(self, seq: bytes, qual: bytes, offsets: np.ndarray, first_unit: int = 0) -> None:
+        """Host reads (staged to HBM in batches; synchronous); first_unit counts units (pairs of a paired handle)."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        check(lib().speq_bootstrap_add_reads(self._h, seq, qual, _u64p(off), len(off) - 1, first_unit))
+
+    def add_device(self, d_seq: int, d_qual: int, d_offsets: int, n_reads: int, first_unit: int = 0,
+                   stream: int = 0) -> None:
+        """HBM-resident reads (raw device pointers, like DeviceIndex.scan_device); asynchronous on `stream`."""
+        check(lib().speq_bootstrap_add_reads_device(self._h, d_seq or None, d_qual or None, d_offsets or None, n_reads,
+                                                    first_unit, stream or None))
+
+    def finalize(self):
+        """(counts [B + 1, G + 2] u64, weights [B + 1, G] f64 or None) of everything added so far."""
+        counts = np.zeros((self.replicates + 1, self.n_groups + 2), dtype=np.uint64)
+        w = np.zeros((self.replicates + 1, self.n_groups), dtype=np.float64) if self.local else None
+        check(lib().speq_bootstrap_finalize(self._h, _u64p(counts),
+                                            w.ctypes.data_as(C.POINTER(C.c_double)) if w is not None else None))
+        return counts, w
+
+    def info(self) -> dict:
+        """{"replicates", "lds_path" (the last add accumulated in LDS), "units_added"}."""
+        r, l, u = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        check(lib().speq_bootstrap_info(self._h, C.byref(r), C.byref(l), C.byref(u)))
+        return {"replicates": r.value, "lds_path": bool(l.value), "units_added": u.value}
+
+    def close(self):
+        if self._h:
+            lib().speq_bootstrap_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bootstrap_summary(counts: np.ndarray, weights: Optional[np.ndarray], u_ref, tot_ref, unique_scale: float = 1.0,
+                      level: float = 0.95) -> list[dict]:
+    """Per group {"estimate", "mean", "se", "lo", "hi", "used"} of a bootstrap's matrices (speq_bootstrap_summary; host
+    only): the percentage of the sample and the spread of the replicates' percentages."""
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    B, G = c.shape[0] - 1, c.shape[1] - 2
+    w = np.ascontiguousarray(weights, dtype=np.float64) if weights is not None else None
+    ur = np.ascontiguousarray(u_ref, dtype=np.uint64)
+    tr = np.ascontiguousarray(tot_ref, dtype=np.uint64)
+    out = (BootstrapCI * max(G, 1))()
+    check(lib().speq_bootstrap_summary(_u64p(c), w.ctypes.data_as(C.POINTER(C.c_double)) if w is not None else None, B,
+                                       G, _u64p(ur), _u64p(tr), unique_scale, level, out))
+    return [{f: getattr(out[g], f) for f in ("estimate", "mean", "se", "lo", "hi", "used")} for g in range(G)]
 
 
 class Comm:

@@ -63,6 +63,13 @@ const char* HELP =
     "                            its unique k-mers (markers) the reads cover and how deep: name, markers, observed,\n"
     "                            breadth, hits, mean_depth, expected_breadth, max_depth, d0..d7 (tab-separated); a\n"
     "                            breadth far below expected_breadth means copies of few k-mers, not the variant\n"
+    "      --bootstrap FILE      scan: after the scan, one more pass over the reads resamples them (Poisson bootstrap\n"
+    "                            of the reads, or pairs) and writes FILE: name, percent, mean, se, lo, hi, used\n"
+    "                            (tab-separated): the interval of each group's initial percentage, the first vector\n"
+    "                            the run prints, from unique k-mers; the EM-refined percentages are not covered\n"
+    "      --bootstrap-replicates N  resamplings, 1..1024 (default 200)\n"
+    "      --bootstrap-seed S    seed of the resampling weights (default 1)\n"
+    "      --bootstrap-level L   two-sided level of lo..hi, in (0,1) (default 0.95)\n"
     "one process per GPU: run under a launcher that sets WORLD_SIZE > 1, RANK and LOCAL_RANK (e.g. torchrun\n"
     "--no-python bin/speq scan ...): each rank scans its share of the reads on GPU $LOCAL_RANK and the counts are\n"
     "summed with RCCL; rank 0 prints and writes the results ($SPEQ_RENDEZVOUS: the id file, default under /tmp)\n";
@@ -159,6 +166,10 @@ CmdArguments parse(int argc, char** argv) {
         }
         else if (allow_reads && opt == "--group-sets") a.out_file_group_sets = value();
         else if (allow_reads && opt == "--marker-coverage") a.out_file_marker_coverage = value();
+        else if (allow_reads && opt == "--bootstrap") a.out_file_bootstrap = value();
+        else if (allow_reads && opt == "--bootstrap-replicates") a.bootstrap_replicates = to_number<unsigned>(opt, value());
+        else if (allow_reads && opt == "--bootstrap-seed") a.bootstrap_seed = to_number<uint64_t>(opt, value());
+        else if (allow_reads && opt == "--bootstrap-level") a.bootstrap_level = to_number<double>(opt, value());
         else if (allow_reads && opt == "--max-em-iterations") a.max_em_iterations = to_number<unsigned>(opt, value());
         else throw ParseError("Unknown option " + opt + ". In case this is meant to be a non-option/argument/parameter, "
                               "please specify the start of non-options with '--'.");
@@ -172,6 +183,13 @@ CmdArguments parse(int argc, char** argv) {
         throw ParseError("Validation failed for option -t/--threads: Value " + std::to_string(a.threads) +
                          " is not in range [2," + std::to_string(hw) + "].");
     if (a.kmer < 1) throw ParseError("Validation failed for option -k/--kmer: must be >= 1");
+    if (a.bootstrap_replicates < 1 || a.bootstrap_replicates > SPEQ_BOOTSTRAP_MAX_REPLICATES)
+        throw ParseError("Validation failed for option --bootstrap-replicates: Value " +
+                         std::to_string(a.bootstrap_replicates) + " is not in range [1," +
+                         std::to_string(SPEQ_BOOTSTRAP_MAX_REPLICATES) + "].");
+    if (!(a.bootstrap_level > 0.0 && a.bootstrap_level < 1.0))
+        throw ParseError("Validation failed for option --bootstrap-level: Value " + std::to_string(a.bootstrap_level) +
+                         " is not in range (0,1).");
     if (a.prefix_q > 13) throw ParseError("Validation failed for option --prefix-q: must be <= 13");
     if (a.is_scanner) {
         check_in_file(a.in_file_reads_path_1);
@@ -193,6 +211,7 @@ CmdArguments parse(int argc, char** argv) {
     check_out_file(a.out_file_path, a.is_force);
     if (!a.out_file_group_sets.empty()) check_out_file(a.out_file_group_sets, a.is_force);
     if (!a.out_file_marker_coverage.empty()) check_out_file(a.out_file_marker_coverage, a.is_force);
+    if (!a.out_file_bootstrap.empty()) check_out_file(a.out_file_bootstrap, a.is_force);
     a.is_parsed = true;
     return a;
 }
@@ -555,6 +574,37 @@ void write_marker_coverage(const CmdArguments& a, speq_device_index* d, const sp
     }
 }
 
+// FILE of --bootstrap: a header line, then per group (groupings order) its name, the run's initial percentage, and over
+// the replicates' percentages their mean, standard deviation (the bootstrap standard error), the lo and hi order
+// statistics of the level, and how many replicates had a passing window at all.
+void write_bootstrap(const CmdArguments& a, speq_device_index* d, const speq_scan_params& prm,
+                     const std::vector<std::string>& names, const std::vector<uint64_t>& u_ref,
+                     const std::vector<uint64_t>& tot_ref) {
+    const size_t G = names.size();
+    const uint32_t B = a.bootstrap_replicates;
+    const bool local = prm.mode == SPEQ_MODE_LOCAL;
+    std::vector<uint64_t> counts((size_t)(B + 1) * (G + 2), 0);
+    std::vector<double> weights(local ? std::max<size_t>((size_t)(B + 1) * G, 1) : 0, 0.0);
+    ok(speq_bootstrap_fastq(d, a.in_file_reads_path_1.c_str(),
+                            a.in_file_reads_path_2.empty() ? nullptr : a.in_file_reads_path_2.c_str(), &prm, B,
+                            a.bootstrap_seed, a.threads, counts.data(), local ? weights.data() : nullptr, nullptr),
+       "bootstrapping the reads");
+    std::vector<speq_bootstrap_ci> ci(std::max<size_t>(G, 1));
+    const double scale = local ? 1.0 : 1.0 / std::pow(a.fixed_accuracy, (double)a.kmer);
+    ok(speq_bootstrap_summary(counts.data(), local ? weights.data() : nullptr, B, (uint32_t)G, u_ref.data(),
+                              tot_ref.data(), scale, a.bootstrap_level, ci.data()),
+       "summarising the bootstrap");
+    std::ofstream of(a.out_file_bootstrap);
+    if (!of) throw CApiError("cannot write " + a.out_file_bootstrap.string());
+    of << "name\tpercent\tmean\tse\tlo\thi\tused\n";
+    for (size_t g = 0; g < G; ++g) {
+        char buf[400];
+        std::snprintf(buf, sizeof buf, "\t%.6f\t%.6f\t%.6f\t%.6f\t%.6f\t%llu\n", ci[g].estimate, ci[g].mean, ci[g].se,
+                      ci[g].lo, ci[g].hi, (unsigned long long)ci[g].used);
+        of << names[g] << buf;
+    }
+}
+
 int run_scan(CmdArguments& a) {
     PhaseClock phase;
     Dist dd = dist_from_env(a);
@@ -813,6 +863,13 @@ int run_scan(CmdArguments& a) {
     if (!a.out_file_marker_coverage.empty()) {
         write_marker_coverage(a, d, prm, h.names);
         phase("marker coverage");
+    }
+    // --bootstrap: one more pass over the same reads, placed like --group-sets; mode, pairing, k, cutoff and the fixed
+    // accuracy are the run's own. The intervals bound the initial percentages (the first vector printed above), not the
+    // EM-refined ones: those would need one histogram per replicate.
+    if (!a.out_file_bootstrap.empty()) {
+        write_bootstrap(a, d, prm, h.names, u_ref, tot_ref);
+        phase("bootstrap");
     }
     // The device replica, its pinned pipeline slots and the index are left to process exit: unpinning and freeing
     // them explicitly costs ~0.07 s and the process ends right after this.

@@ -574,6 +574,7 @@ struct Work {
     uint64_t n = 0;      // records (pairs when paired) to parse
     bool split = false;  // cut by find_cut: records not yet counted or checked
     uint64_t seq = 0;    // block number in file order (the rank sharding deals blocks by it)
+    uint64_t first = 0;  // sequential reader only: the block's first record (both mates counted) in file order
 };
 
 // Which blocks this process scans: block b belongs to shard b % n (one process per GPU, `speq scan` under a
@@ -619,6 +620,12 @@ struct Sink {
     // a slot for raw text only (s.seq; submit_raw or submit(s, 0) next)
     virtual void acquire_raw(speq_slot& s, uint64_t bytes) { acquire(s, bytes, 1); }
     virtual void submit(const speq_slot& s, uint64_t records) = 0;  // records == 0 releases the slot
+    // submit() of a host-parsed block of the sequential reader, with the index of its first record in the input (both
+    // mates counted): for sinks whose result depends on where in the file a record stands
+    virtual void submit_at(const speq_slot& s, uint64_t records, uint64_t first_record) {
+        (void)first_record;
+        submit(s, records);
+    }
     // raw four-line FASTQ text (file 1's block, then file 2's) in s.seq, n records per file
     // host1 / host2 non-null: the blocks are copied from there (the file's mapping), not from s.seq
     virtual void submit_raw(const speq_slot& s, uint64_t len1, uint64_t len2, uint64_t n, bool paired,
@@ -902,6 +909,24 @@ struct MarkerSink final : HostSink {
     }
 };
 
+// The read bootstrap of every host-parsed block (speq_bootstrap_add_reads) into one handle: a unit's weights depend on
+// its index in the file, which the block's first record gives; the sums are integers (and f64 atomics in local mode),
+// so the blocks' order does not matter to the counts.
+struct BootstrapSink final : HostSink {
+    speq_bootstrap* b;
+    uint32_t per;  // records per unit
+    BootstrapSink(speq_bootstrap* handle, bool paired) : b(handle), per(paired ? 2u : 1u) {}
+    void submit(const speq_slot& s, uint64_t records) override {
+        Release rel{*this, s.slot};
+        if (records != 0) throw std::logic_error("the bootstrap sink needs the block's first record");
+    }
+    void submit_at(const speq_slot& s, uint64_t records, uint64_t first_record) override {
+        Release rel{*this, s.slot};
+        if (records == 0) return;
+        check_rc(speq_bootstrap_add_reads(b, s.seq, s.qual, s.offsets, records, first_record / per));
+    }
+};
+
 // Pinned slot size of speq_scan_fastq's pipeline: a block pair of up to 12 MiB per file plus one record usually
 // fits (larger blocks grow their slot once: speq_pipeline_reserve).
 constexpr uint64_t SLOT_BYTES = 16ull << 20;
@@ -1144,7 +1169,7 @@ StreamTotals run_stream(const char* path1, const char* path2, uint32_t threads, 
                 sh.cv_get.notify_all();
                 return;
             }
-            for (uint64_t b = 0;; ++b) {
+            for (uint64_t b = 0, first = 0;; ++b) {
                 Work w;
                 w.b1 = c1.next(BLOCK_RECORDS, BLOCK_BYTES);
                 w.n = w.b1.n;
@@ -1154,6 +1179,8 @@ StreamTotals run_stream(const char* path1, const char* path2, uint32_t threads, 
                 }
                 const bool last = w.n == 0 || (paired && w.b2.n < w.b1.n);
                 w.seq = b;
+                w.first = first;
+                first += paired ? 2 * w.n : w.n;
                 if (w.n && shard.mine(b) && !push(std::move(w))) return;
                 if (last) break;
             }
@@ -1313,7 +1340,7 @@ StreamTotals run_stream(const char* path1, const char* path2, uint32_t threads, 
                     sink.submit(s, 0);
                     throw;
                 }
-                sink.submit(s, recs);
+                sink.submit_at(s, recs, w.first);
                 sh.records += recs;
                 sh.bases += out;
                 sh.batches += 1;
@@ -1568,6 +1595,37 @@ extern "C" int speq_markers_fastq(speq_device_index* d, const char* path1, const
         fill_stats(stats, tot, t0);
     });
     speq_markers_free(m);
+    return rc;
+}
+
+extern "C" int speq_bootstrap_fastq(speq_device_index* d, const char* path1, const char* path2,
+                                    const speq_scan_params* params, uint32_t replicates, uint64_t seed,
+                                    uint32_t threads, uint64_t* counts, double* weights, speq_stream_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    speq_scan_params p{};
+    int rc = speq::guarded([&] {
+        const char* who = "speq_bootstrap_fastq";
+        if (!params) throw std::invalid_argument(std::string(who) + ": null params");
+        speq::check_report_k(who, params->k);
+        if (replicates < 1 || replicates > SPEQ_BOOTSTRAP_MAX_REPLICATES)
+            throw std::invalid_argument(std::string(who) + ": replicates must be in [1, " +
+                                        std::to_string(SPEQ_BOOTSTRAP_MAX_REPLICATES) + "]");
+        if (!d || !path1 || !counts || (params->mode == SPEQ_MODE_LOCAL && !weights))
+            throw std::invalid_argument(std::string(who) + ": null argument");
+        p = *params;
+        p.paired = path2 != nullptr;
+    });
+    if (rc != SPEQ_OK) return rc;
+    speq_bootstrap* b = nullptr;
+    rc = speq_bootstrap_create(d, &p, replicates, seed, &b);  // (its own status: SPEQ_E_NOMEM)
+    if (rc != SPEQ_OK) return rc;
+    rc = speq::guarded([&] {
+        BootstrapSink sink(b, p.paired != 0);
+        const StreamTotals tot = run_stream(path1, path2, threads, sink, false, false);
+        check_rc(speq_bootstrap_finalize(b, counts, p.mode == SPEQ_MODE_LOCAL ? weights : nullptr));
+        fill_stats(stats, tot, t0);
+    });
+    speq_bootstrap_free(b);
     return rc;
 }
 
