@@ -281,6 +281,28 @@ typedef struct { double estimate, mean, se, lo, hi; uint64_t used; } speq_bootst
 int speq_bootstrap_summary(const uint64_t* counts, const double* weights, uint32_t replicates, uint32_t n_groups,
                            const uint64_t* u_ref, const uint64_t* tot_ref, double unique_scale, double level,
                            speq_bootstrap_ci* out /* [G] */);
+/* The same statistics over a given percentage matrix, f64 [B + 1][G] (the EM-refined percentages of
+ * speq_em_rows_refine): row b = 1 .. B is a replicate, left out where used_mask[b] == 0 (u8 [B + 1]; [0] is not read);
+ * estimate is the vector `estimate`, or row 0 when it is NULL. */
+int speq_bootstrap_summary_percent(const double* percent, const double* estimate, const uint8_t* used_mask,
+                                   uint32_t replicates, uint32_t n_groups, double level,
+                                   speq_bootstrap_ci* out /* [G] */);
+/* One EM histogram per replicate, filled by the adds in the same pass. `em` must be finalized, of the
+ * same replica and group count as b, and b must have had no reads added and no histogram attached; otherwise
+ * SPEQ_E_ARG. Uploads em's interval -> row map and allocates the u64 [n_rows][B + 1] matrix (SPEQ_E_NOMEM when it does
+ * not fit); blocking. em itself is not kept: it may be freed afterwards. From then on every add also adds, per unit u
+ * and replicate b, w(u, b) * (u's multi-group windows whose interval em holds, per merged row); a multi-group window
+ * whose interval em does not hold is counted in `missed`. The counts and weights of b are what they are without. */
+struct speq_em;
+int speq_bootstrap_attach_em(speq_bootstrap* b, const struct speq_em* em);
+/* *n_rows: em's merged rows; *lds_rows: H, how many of them (the most frequent in the sample) a block accumulates in
+ * LDS: min(n_rows, floor((64 KiB - 4 wave_bytes(k) - the counters' cells when they take the LDS path) / (8 (B + 1)))).
+ * SPEQ_E_ARG without an attached histogram. */
+int speq_bootstrap_em_info(const speq_bootstrap* b, uint64_t* n_rows, uint32_t* lds_rows);
+/* Like speq_bootstrap_finalize (waits; repeatable): mult is u64 [B + 1][n_rows], row b the multiplicities of replicate
+ * b in the order of speq_em_rows, so mult[0] equals em's row_mult when the reads are those of em's scan and *missed
+ * (may be NULL) is 0. */
+int speq_bootstrap_finalize_em(speq_bootstrap* b, uint64_t* mult, uint64_t* missed);
 
 /* ---- reference-uniqueness pass (replaces _async_count_unique_kmers_per_group, fm_scanner.cpp:1476-1576)
  * For every window of every text (fwd and rc of each record): Tot_ref[g] += 1, and U_ref[g] += 1 iff
@@ -345,6 +367,29 @@ int speq_em_rows(const speq_em* em, uint64_t* n_rows, uint64_t* n_entries, uint6
  * unique[G] (the U[g] counters of the same scan, i.e. its single-group windows). */
 int speq_em_step(const speq_em* em, const double* percent, const int32_t* group_counts, const uint64_t* unique,
                  double* next);
+/* Test accessor, call-twice like speq_em_rows: *n recorded intervals (speq_em_info's n_intervals), lo[n] their SA
+ * interval starts ascending, row[n] the index in speq_em_rows' order of the merged row each went into. Fails with
+ * SPEQ_E_ARG before speq_em_finalize. */
+int speq_em_intervals(const speq_em* em, uint64_t* n, uint32_t* lo, uint32_t* row);
+/* speq_em_step without a handle or a GPU, over rows as speq_em_rows returns them (row_ptr[n_rows + 1] ascending from
+ * 0, groups below n_groups) with the multiplicities mult[n_rows] in row_mult's place: the same sweep, so with
+ * mult = row_mult the same bits. */
+int speq_em_rows_step(uint32_t n_groups, uint64_t n_rows, const uint64_t* row_ptr, const uint32_t* col_group,
+                      const uint32_t* col_count, const uint64_t* mult, const double* percent,
+                      const int32_t* group_counts, const uint64_t* unique, double* next);
+/* The refinement loop of `speq scan` for every row b of a bootstrap's matrices (mult u64 [B + 1][n_rows] of
+ * speq_bootstrap_finalize_em, counts u64 [B + 1][G + 2], weights f64 [B + 1][G] or NULL): unique_totals = weights[b],
+ * or counts[b][2 ..] * unique_scale; total = counts[b][0]; percent = unique_to_percent(unique_totals, total, u_ref,
+ * tot_ref); then, while the largest |change| of a step is above precision and fewer than max_iterations steps were
+ * made: next = the step over mult[b] with unique = counts[b][2 ..], percent = unique_to_percent(unique_totals, total,
+ * unique_totals, next). percent_out is f64 [B + 1][G], iterations_out u32 [B + 1] the steps made. A row with
+ * counts[b][0] == 0 gets zeros and 0 steps. The rows are refined side by side on the library's worker pool (at most
+ * 16 threads), each one's sweep adding its chunks in chunk order: the result does not depend on the thread count. */
+int speq_em_rows_refine(uint32_t n_groups, uint64_t n_rows, const uint64_t* row_ptr, const uint32_t* col_group,
+                        const uint32_t* col_count, uint32_t replicates, const uint64_t* mult, const uint64_t* counts,
+                        const double* weights, double unique_scale, const uint64_t* u_ref, const uint64_t* tot_ref,
+                        const int32_t* group_counts, double precision, uint32_t max_iterations, double* percent_out,
+                        uint32_t* iterations_out);
 void speq_em_free(speq_em* em);
 
 /* ---- streaming scan: pinned host slots, H2D on a copy stream overlapped with the kernel ----
@@ -424,6 +469,12 @@ int speq_markers_fastq(speq_device_index* d, const char* path1, const char* path
 int speq_bootstrap_fastq(speq_device_index* d, const char* path1, const char* path2, const speq_scan_params* params,
                          uint32_t replicates, uint64_t seed, uint32_t threads, uint64_t* counts, double* weights,
                          speq_stream_stats* stats);
+/* The same with the finalized histogram em attached (speq_bootstrap_attach_em): also mult u64 [B + 1][n_rows] and
+ * *missed (may be NULL) of speq_bootstrap_finalize_em; independent of `threads` as well. */
+int speq_bootstrap_em_fastq(speq_device_index* d, const speq_em* em, const char* path1, const char* path2,
+                            const speq_scan_params* params, uint32_t replicates, uint64_t seed, uint32_t threads,
+                            uint64_t* counts, double* weights, uint64_t* mult, uint64_t* missed,
+                            speq_stream_stats* stats);
 
 /* ---- several GPUs in one process ----
  * Reads shard across the GPUs of a node, the index is replicated (one speq_device_index per GPU, opened from the

@@ -6,6 +6,7 @@ ibharvey/speq (C++/SeqAn3); see DESIGN.md for the path, the boundary and the dat
 """
 from ._lib import SpeqError, lib  # noqa: F401  (raises if libspeq_scan.so is missing)
 from .api import (SPEQ_MODE_GLOBAL, SPEQ_MODE_LOCAL, Bootstrap, Comm, DeviceIndex, EmHistogram, FmIndex, Groupings, MarkerCoverage, Markers, Node,  # noqa: F401,E501
-                  Pipeline, ReadReport, ScanResult, bootstrap_summary, em_refine, file_to_map, pack_records, unique_to_percent)
+                  Pipeline, ReadReport, ScanResult, bootstrap_summary, bootstrap_summary_percent, em_refine, em_rows_refine,
+                  em_rows_step, file_to_map, pack_records, unique_to_percent)
 
 __version__ = "0.1.0"

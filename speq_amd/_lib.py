@@ -119,6 +119,13 @@ SIGNATURES = {
     "speq_bootstrap_weight": (C.c_uint32, [C.c_uint64, C.c_uint64, C.c_uint32]),
     "speq_bootstrap_summary": (C.c_int, [_U64P, _F64P, C.c_uint32, C.c_uint32, _U64P, _U64P, C.c_double, C.c_double,
                                          C.POINTER(BootstrapCI)]),
+    "speq_bootstrap_summary_percent": (C.c_int, [_F64P, _F64P, _U8P, C.c_uint32, C.c_uint32, C.c_double,
+                                                 C.POINTER(BootstrapCI)]),
+    "speq_bootstrap_attach_em": (C.c_int, [_P, _P]),
+    "speq_bootstrap_em_info": (C.c_int, [_P, _U64P, _U32P]),
+    "speq_bootstrap_finalize_em": (C.c_int, [_P, _U64P, _U64P]),
+    "speq_bootstrap_em_fastq": (C.c_int, [_P, _P, C.c_char_p, C.c_char_p, C.POINTER(ScanParams), C.c_uint32,
+                                          C.c_uint64, C.c_uint32, _U64P, _F64P, _U64P, _U64P, C.POINTER(StreamStats)]),
     "speq_ref_unique": (C.c_int, [_P, C.c_uint32, _U64P, _U64P]),
     "speq_ref_unique_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P]),
     "speq_comm_unique_id": (C.c_int, [_P]),
@@ -136,6 +143,10 @@ SIGNATURES = {
     "speq_em_info": (C.c_int, [_P, _U64P, _U64P, _U64P]),
     "speq_em_rows": (C.c_int, [_P, _U64P, _U64P, _U64P, _U64P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "speq_em_step": (C.c_int, [_P, _F64P, _I32P, _U64P, _F64P]),
+    "speq_em_intervals": (C.c_int, [_P, _U64P, _U32P, _U32P]),
+    "speq_em_rows_step": (C.c_int, [C.c_uint32, C.c_uint64, _U64P, _U32P, _U32P, _U64P, _F64P, _I32P, _U64P, _F64P]),
+    "speq_em_rows_refine": (C.c_int, [C.c_uint32, C.c_uint64, _U64P, _U32P, _U32P, C.c_uint32, _U64P, _U64P, _F64P,
+                                      C.c_double, _U64P, _U64P, _I32P, C.c_double, C.c_uint32, _F64P, _U32P]),
     "speq_em_free": (None, [_P]),
     "speq_pipeline_create": (C.c_int, [_P, C.POINTER(ScanParams), _P, C.c_uint64, C.c_uint64, C.c_uint32,
                                        C.POINTER(_P)]),

@@ -23,7 +23,7 @@ import numpy as np
 from ._lib import (MARKER_BINS, SPEQ_MODE_GLOBAL, SPEQ_MODE_LOCAL, BootstrapCI, BuildOpts, IndexInfo,  # noqa: F401
                    ScanParams, Slot, SpeqError, StreamStats, check, lib)
 
-__all__ = ["FmIndex", "DeviceIndex", "Node", "Pipeline", "ScanResult", "ReadReport", "Markers", "MarkerCoverage", "Bootstrap", "bootstrap_summary", "Groupings", "EmHistogram", "Comm", "file_to_map", "unique_to_percent",
+__all__ = ["FmIndex", "DeviceIndex", "Node", "Pipeline", "ScanResult", "ReadReport", "Markers", "MarkerCoverage", "Bootstrap", "bootstrap_summary", "bootstrap_summary_percent", "em_rows_step", "em_rows_refine", "Groupings", "EmHistogram", "Comm", "file_to_map", "unique_to_percent",
            "em_refine", "pack_records", "SpeqError", "SPEQ_MODE_GLOBAL", "SPEQ_MODE_LOCAL"]
 
 
@@ -353,6 +353,23 @@ class DeviceIndex:
                                          w.ctypes.data_as(C.POINTER(C.c_double)) if w is not None else None, None))
         return counts, w
 
+    def bootstrap_em_fastq(self, em: "EmHistogram", path1: str, path2: Optional[str] = None, k: int = 21,
+                           replicates: int = 200, seed: int = 1, phred_cutoff: int = 30, local: bool = False,
+                           threads: int = 4):
+        """bootstrap_fastq with the finalized histogram `em` attached (speq_bootstrap_em_fastq): (counts, weights,
+        mult [B + 1, n_rows] u64, missed)."""
+        G = self.n_groups
+        counts = np.zeros((replicates + 1, G + 2), dtype=np.uint64)
+        w = np.zeros((replicates + 1, G), dtype=np.float64) if local else None
+        mult = np.zeros((replicates + 1, em.n_rows()), dtype=np.uint64)
+        missed = C.c_uint64()
+        p = ScanParams(k, phred_cutoff, int(path2 is not None), SPEQ_MODE_LOCAL if local else SPEQ_MODE_GLOBAL)
+        check(lib().speq_bootstrap_em_fastq(self._h, em._h, path1.encode(), path2.encode() if path2 else None,
+                                            C.byref(p), replicates, seed, threads, _u64p(counts),
+                                            w.ctypes.data_as(C.POINTER(C.c_double)) if w is not None else None,
+                                            _u64p(mult), C.byref(missed), None))
+        return counts, w, mult, missed.value
+
     AX_STATS_KEYS = ("wave_iters", "lookup_lanes", "run_lanes", "lookup_waves", "run_waves", "run_windows",
                      "deferred", "filter_pass", "p2_probes", "p2_verify", "chunks", "segments", "qual_bytes",
                      "run_tallied", "run_granules", "refills", "busy_1_4", "busy_5_16", "busy_17_32", "busy_33_64",
@@ -549,6 +566,25 @@ class Bootstrap:
                                             w.ctypes.data_as(C.POINTER(C.c_double)) if w is not None else None))
         return counts, w
 
+    def attach_em(self, em: "EmHistogram") -> None:
+        """One EM histogram per replicate (speq_bootstrap_attach_em): before the first add, with the finalized
+        histogram of the same replica; the adds then also fill the multiplicities finalize_em returns."""
+        check(lib().speq_bootstrap_attach_em(self._h, em._h))
+
+    def em_info(self) -> dict:
+        """{"n_rows", "lds_rows" (the most frequent rows, accumulated per block in LDS)}."""
+        n, h = C.c_uint64(), C.c_uint32()
+        check(lib().speq_bootstrap_em_info(self._h, C.byref(n), C.byref(h)))
+        return {"n_rows": n.value, "lds_rows": h.value}
+
+    def finalize_em(self):
+        """(mult [B + 1, n_rows] u64 in EmHistogram.rows() order, missed) of everything added so far."""
+        n = self.em_info()["n_rows"]
+        mult = np.zeros((self.replicates + 1, n), dtype=np.uint64)
+        missed = C.c_uint64()
+        check(lib().speq_bootstrap_finalize_em(self._h, _u64p(mult), C.byref(missed)))
+        return mult, missed.value
+
     def info(self) -> dict:
         """{"replicates", "lds_path" (the last add accumulated in LDS), "units_added"}."""
         r, l, u = C.c_uint32(), C.c_uint32(), C.c_uint64()
@@ -579,6 +615,24 @@ def bootstrap_summary(counts: np.ndarray, weights: Optional[np.ndarray], u_ref, 
     out = (BootstrapCI * max(G, 1))()
     check(lib().speq_bootstrap_summary(_u64p(c), w.ctypes.data_as(C.POINTER(C.c_double)) if w is not None else None, B,
                                        G, _u64p(ur), _u64p(tr), unique_scale, level, out))
+    return [{f: getattr(out[g], f) for f in ("estimate", "mean", "se", "lo", "hi", "used")} for g in range(G)]
+
+
+def bootstrap_summary_percent(percent: np.ndarray, used, estimate=None, level: float = 0.95) -> list[dict]:
+    """bootstrap_summary's statistics over a percentage matrix [B + 1, G] (speq_bootstrap_summary_percent; host only):
+    used[b] says whether replicate b counts, estimate replaces row 0 as the sample's vector."""
+    p = np.ascontiguousarray(percent, dtype=np.float64)
+    B, G = p.shape[0] - 1, p.shape[1]
+    u = np.ascontiguousarray(used, dtype=np.uint8)
+    if u.shape != (B + 1,):
+        raise ValueError("used has one entry per row of percent")
+    e = np.ascontiguousarray(estimate, dtype=np.float64) if estimate is not None else None
+    if e is not None and e.shape != (G,):
+        raise ValueError("estimate has one entry per group")
+    dp = C.POINTER(C.c_double)
+    out = (BootstrapCI * max(G, 1))()
+    check(lib().speq_bootstrap_summary_percent(p.ctypes.data_as(dp), e.ctypes.data_as(dp) if e is not None else None,
+                                               u.ctypes.data_as(C.POINTER(C.c_uint8)), B, G, level, out))
     return [{f: getattr(out[g], f) for f in ("estimate", "mean", "se", "lo", "hi", "used")} for g in range(G)]
 
 
@@ -752,6 +806,34 @@ class EmHistogram:
         p, g, c = ptr.tolist(), grp.tolist(), cnt.tolist()
         return [(int(mult[r]), tuple(zip(g[p[r]:p[r + 1]], c[p[r]:p[r + 1]]))) for r in range(nr.value)]
 
+    def n_rows(self) -> int:
+        nr = C.c_uint64()
+        check(lib().speq_em_rows(self._h, C.byref(nr), None, None, None, None, None))
+        return nr.value
+
+    def rows_csr(self) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(row_mult, row_ptr, col_group, col_count) as speq_em_rows returns them: what em_rows_step takes."""
+        nr, ne = C.c_uint64(), C.c_uint64()
+        check(lib().speq_em_rows(self._h, C.byref(nr), C.byref(ne), None, None, None, None))
+        mult = np.zeros(nr.value, dtype=np.uint64)
+        ptr = np.zeros(nr.value + 1, dtype=np.uint64)
+        grp = np.zeros(ne.value, dtype=np.uint32)
+        cnt = np.zeros(ne.value, dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        check(lib().speq_em_rows(self._h, None, None, _u64p(mult), _u64p(ptr), grp.ctypes.data_as(u32p),
+                                 cnt.ctypes.data_as(u32p)))
+        return mult, ptr, grp, cnt
+
+    def intervals(self) -> tuple[np.ndarray, np.ndarray]:
+        """Test accessor (speq_em_intervals): (lo, row) of every recorded interval, lo ascending; row indexes
+        rows()."""
+        n = C.c_uint64()
+        check(lib().speq_em_intervals(self._h, C.byref(n), None, None))
+        lo, row = np.zeros(n.value, dtype=np.uint32), np.zeros(n.value, dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        check(lib().speq_em_intervals(self._h, None, lo.ctypes.data_as(u32p), row.ctypes.data_as(u32p)))
+        return lo, row
+
     def step(self, percent, group_counts, unique) -> np.ndarray:
         p = np.ascontiguousarray(percent, dtype=np.float64)
         gc = np.ascontiguousarray(group_counts, dtype=np.int32)
@@ -829,6 +911,58 @@ class Node:
     def close(self):
         for d in self.devices:
             d.close()
+
+
+def _csr(n_groups: int, row_ptr, col_group, col_count):
+    ptr = np.ascontiguousarray(row_ptr, dtype=np.uint64)
+    grp = np.ascontiguousarray(col_group, dtype=np.uint32)
+    cnt = np.ascontiguousarray(col_count, dtype=np.uint32)
+    if ptr.ndim != 1 or len(ptr) < 1 or len(grp) != len(cnt) or (len(ptr) > 0 and int(ptr[-1]) != len(grp)):
+        raise ValueError("row_ptr must end at the number of (group, count) entries")
+    u32p = C.POINTER(C.c_uint32)
+    return ptr, grp, cnt, (n_groups, len(ptr) - 1, _u64p(ptr), grp.ctypes.data_as(u32p), cnt.ctypes.data_as(u32p))
+
+
+def em_rows_step(n_groups: int, row_ptr, col_group, col_count, mult, percent, group_counts, unique) -> np.ndarray:
+    """EmHistogram.step over given CSR rows with the multiplicities `mult` (speq_em_rows_step; host only)."""
+    ptr, grp, cnt, args = _csr(n_groups, row_ptr, col_group, col_count)
+    m = np.ascontiguousarray(mult, dtype=np.uint64)
+    p = np.ascontiguousarray(percent, dtype=np.float64)
+    gc = np.ascontiguousarray(group_counts, dtype=np.int32)
+    u = np.ascontiguousarray(unique, dtype=np.uint64)
+    if m.shape != (len(ptr) - 1,) or p.shape != (n_groups,) or gc.shape != (n_groups,) or u.shape != (n_groups,):
+        raise ValueError("mult has one entry per row; percent, group_counts and unique one per group")
+    nxt = np.zeros(n_groups, dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    check(lib().speq_em_rows_step(*args, _u64p(m), p.ctypes.data_as(dp), gc.ctypes.data_as(C.POINTER(C.c_int32)),
+                                  _u64p(u), nxt.ctypes.data_as(dp)))
+    return nxt
+
+
+def em_rows_refine(n_groups: int, row_ptr, col_group, col_count, mult, counts, weights, u_ref, tot_ref, group_counts,
+                   unique_scale: float = 1.0, precision: float = 1e-6, max_iterations: int = 1000):
+    """The refinement loop for every row of a bootstrap's matrices (speq_em_rows_refine; host only): mult [B + 1,
+    n_rows], counts [B + 1, G + 2], weights [B + 1, G] or None. Returns (percent [B + 1, G] f64, iterations [B + 1])."""
+    ptr, grp, cnt, args = _csr(n_groups, row_ptr, col_group, col_count)
+    G, n_rows = n_groups, len(ptr) - 1
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    B = c.shape[0] - 1
+    m = np.ascontiguousarray(mult, dtype=np.uint64)
+    w = np.ascontiguousarray(weights, dtype=np.float64) if weights is not None else None
+    ur = np.ascontiguousarray(u_ref, dtype=np.uint64)
+    tr = np.ascontiguousarray(tot_ref, dtype=np.uint64)
+    gc = np.ascontiguousarray(group_counts, dtype=np.int32)
+    if c.ndim != 2 or B < 0 or c.shape[1] != G + 2 or m.shape != (B + 1, n_rows) or \
+            (w is not None and w.shape != (B + 1, G)) or ur.shape != (G,) or tr.shape != (G,) or gc.shape != (G,):
+        raise ValueError("shapes: mult [B + 1, n_rows], counts [B + 1, G + 2], weights [B + 1, G], G-vectors")
+    out = np.zeros((B + 1, G), dtype=np.float64)
+    its = np.zeros(B + 1, dtype=np.uint32)
+    dp = C.POINTER(C.c_double)
+    check(lib().speq_em_rows_refine(*args, B, _u64p(m), _u64p(c), w.ctypes.data_as(dp) if w is not None else None,
+                                    unique_scale, _u64p(ur), _u64p(tr), gc.ctypes.data_as(C.POINTER(C.c_int32)),
+                                    precision, max_iterations, out.ctypes.data_as(dp),
+                                    its.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return out, its
 
 
 def em_refine(step, unique_totals, total, percent0, precision: float = 1e-6, max_iterations: int = 1000):

@@ -39,6 +39,7 @@ struct CmdArguments {  // include/arg_parse.h:10-28
     std::filesystem::path out_file_group_sets{};  // --group-sets: the pairs' (reads') group sets, the real fusion map
     std::filesystem::path out_file_marker_coverage{};  // --marker-coverage: per group, its markers and their depths
     std::filesystem::path out_file_bootstrap{};   // --bootstrap: per group, the percentage and its bootstrap interval
+    std::filesystem::path out_file_bootstrap_em{};  // --bootstrap-em: the same for the EM-refined percentages
     unsigned int bootstrap_replicates{200};       // --bootstrap-replicates
     uint64_t bootstrap_seed{1};                   // --bootstrap-seed
     double bootstrap_level{0.95};                 // --bootstrap-level

@@ -67,6 +67,9 @@ const char* HELP =
     "                            of the reads, or pairs) and writes FILE: name, percent, mean, se, lo, hi, used\n"
     "                            (tab-separated): the interval of each group's initial percentage, the first vector\n"
     "                            the run prints, from unique k-mers; the EM-refined percentages are not covered\n"
+    "      --bootstrap-em FILE   scan: the same pass also fills one EM histogram per resampling and refines each with\n"
+    "                            the run's --precision-cutoff and --max-em-iterations; FILE has the same columns for\n"
+    "                            the EM-refined percentages, the vector written to -o\n"
     "      --bootstrap-replicates N  resamplings, 1..1024 (default 200)\n"
     "      --bootstrap-seed S    seed of the resampling weights (default 1)\n"
     "      --bootstrap-level L   two-sided level of lo..hi, in (0,1) (default 0.95)\n"
@@ -167,6 +170,7 @@ CmdArguments parse(int argc, char** argv) {
         else if (allow_reads && opt == "--group-sets") a.out_file_group_sets = value();
         else if (allow_reads && opt == "--marker-coverage") a.out_file_marker_coverage = value();
         else if (allow_reads && opt == "--bootstrap") a.out_file_bootstrap = value();
+        else if (allow_reads && opt == "--bootstrap-em") a.out_file_bootstrap_em = value();
         else if (allow_reads && opt == "--bootstrap-replicates") a.bootstrap_replicates = to_number<unsigned>(opt, value());
         else if (allow_reads && opt == "--bootstrap-seed") a.bootstrap_seed = to_number<uint64_t>(opt, value());
         else if (allow_reads && opt == "--bootstrap-level") a.bootstrap_level = to_number<double>(opt, value());
@@ -212,6 +216,7 @@ CmdArguments parse(int argc, char** argv) {
     if (!a.out_file_group_sets.empty()) check_out_file(a.out_file_group_sets, a.is_force);
     if (!a.out_file_marker_coverage.empty()) check_out_file(a.out_file_marker_coverage, a.is_force);
     if (!a.out_file_bootstrap.empty()) check_out_file(a.out_file_bootstrap, a.is_force);
+    if (!a.out_file_bootstrap_em.empty()) check_out_file(a.out_file_bootstrap_em, a.is_force);
     a.is_parsed = true;
     return a;
 }
@@ -576,33 +581,81 @@ void write_marker_coverage(const CmdArguments& a, speq_device_index* d, const sp
 
 // FILE of --bootstrap: a header line, then per group (groupings order) its name, the run's initial percentage, and over
 // the replicates' percentages their mean, standard deviation (the bootstrap standard error), the lo and hi order
-// statistics of the level, and how many replicates had a passing window at all.
-void write_bootstrap(const CmdArguments& a, speq_device_index* d, const speq_scan_params& prm,
-                     const std::vector<std::string>& names, const std::vector<uint64_t>& u_ref,
-                     const std::vector<uint64_t>& tot_ref) {
-    const size_t G = names.size();
-    const uint32_t B = a.bootstrap_replicates;
-    const bool local = prm.mode == SPEQ_MODE_LOCAL;
-    std::vector<uint64_t> counts((size_t)(B + 1) * (G + 2), 0);
-    std::vector<double> weights(local ? std::max<size_t>((size_t)(B + 1) * G, 1) : 0, 0.0);
-    ok(speq_bootstrap_fastq(d, a.in_file_reads_path_1.c_str(),
-                            a.in_file_reads_path_2.empty() ? nullptr : a.in_file_reads_path_2.c_str(), &prm, B,
-                            a.bootstrap_seed, a.threads, counts.data(), local ? weights.data() : nullptr, nullptr),
-       "bootstrapping the reads");
-    std::vector<speq_bootstrap_ci> ci(std::max<size_t>(G, 1));
-    const double scale = local ? 1.0 : 1.0 / std::pow(a.fixed_accuracy, (double)a.kmer);
-    ok(speq_bootstrap_summary(counts.data(), local ? weights.data() : nullptr, B, (uint32_t)G, u_ref.data(),
-                              tot_ref.data(), scale, a.bootstrap_level, ci.data()),
-       "summarising the bootstrap");
-    std::ofstream of(a.out_file_bootstrap);
-    if (!of) throw CApiError("cannot write " + a.out_file_bootstrap.string());
+// statistics of the level, and how many replicates had a passing window at all. FILE of --bootstrap-em: the same
+// columns for the EM-refined percentages, `percent` being the run's own refined vector (the one written to -o). One
+// pass over the reads serves both files; with --bootstrap-em the finalized histogram `em` of the run is attached, so
+// that the pass fills one histogram per replicate, and every replicate is refined by the run's own loop.
+void write_table(const fs::path& path, const std::vector<std::string>& names, const std::vector<speq_bootstrap_ci>& ci) {
+    std::ofstream of(path);
+    if (!of) throw CApiError("cannot write " + path.string());
     of << "name\tpercent\tmean\tse\tlo\thi\tused\n";
-    for (size_t g = 0; g < G; ++g) {
+    for (size_t g = 0; g < names.size(); ++g) {
         char buf[400];
         std::snprintf(buf, sizeof buf, "\t%.6f\t%.6f\t%.6f\t%.6f\t%.6f\t%llu\n", ci[g].estimate, ci[g].mean, ci[g].se,
                       ci[g].lo, ci[g].hi, (unsigned long long)ci[g].used);
         of << names[g] << buf;
     }
+}
+
+void write_bootstrap(const CmdArguments& a, speq_device_index* d, const speq_scan_params& prm,
+                     const std::vector<std::string>& names, const std::vector<uint64_t>& u_ref,
+                     const std::vector<uint64_t>& tot_ref, const speq_em* em, const std::vector<int32_t>& group_counts,
+                     const std::vector<double>& refined) {
+    const size_t G = names.size();
+    const uint32_t B = a.bootstrap_replicates;
+    const bool local = prm.mode == SPEQ_MODE_LOCAL;
+    const bool with_em = !a.out_file_bootstrap_em.empty();
+    std::vector<uint64_t> counts((size_t)(B + 1) * (G + 2), 0);
+    std::vector<double> weights(local ? std::max<size_t>((size_t)(B + 1) * G, 1) : 0, 0.0);
+    const char* p1 = a.in_file_reads_path_1.c_str();
+    const char* p2 = a.in_file_reads_path_2.empty() ? nullptr : a.in_file_reads_path_2.c_str();
+    uint64_t n_rows = 0, n_entries = 0, missed = 0;
+    std::vector<uint64_t> mult;
+    if (with_em) {
+        ok(speq_em_rows(em, &n_rows, &n_entries, nullptr, nullptr, nullptr, nullptr), "reading the EM histogram");
+        mult.assign(std::max<size_t>((size_t)(B + 1) * n_rows, 1), 0);
+        ok(speq_bootstrap_em_fastq(d, em, p1, p2, &prm, B, a.bootstrap_seed, a.threads, counts.data(),
+                                   local ? weights.data() : nullptr, mult.data(), &missed, nullptr),
+           "bootstrapping the reads");
+        if (missed != 0)
+            throw CApiError("bootstrapping the reads: " + std::to_string(missed) +
+                            " windows lie in intervals that the scan's EM histogram does not hold");
+    } else {
+        ok(speq_bootstrap_fastq(d, p1, p2, &prm, B, a.bootstrap_seed, a.threads, counts.data(),
+                                local ? weights.data() : nullptr, nullptr),
+           "bootstrapping the reads");
+    }
+    std::vector<speq_bootstrap_ci> ci(std::max<size_t>(G, 1));
+    const double scale = local ? 1.0 : 1.0 / std::pow(a.fixed_accuracy, (double)a.kmer);
+    if (!a.out_file_bootstrap.empty()) {
+        ok(speq_bootstrap_summary(counts.data(), local ? weights.data() : nullptr, B, (uint32_t)G, u_ref.data(),
+                                  tot_ref.data(), scale, a.bootstrap_level, ci.data()),
+           "summarising the bootstrap");
+        write_table(a.out_file_bootstrap, names, ci);
+    }
+    if (!with_em) return;
+    std::vector<uint64_t> row_ptr(n_rows + 1, 0);
+    std::vector<uint32_t> grp(std::max<uint64_t>(n_entries, 1)), cnt(std::max<uint64_t>(n_entries, 1));
+    ok(speq_em_rows(em, nullptr, nullptr, nullptr, row_ptr.data(), grp.data(), cnt.data()), "reading the EM histogram");
+    std::vector<double> percent(std::max<size_t>((size_t)(B + 1) * G, 1), 0.0);
+    std::vector<uint32_t> iterations(B + 1, 0);
+    ok(speq_em_rows_refine((uint32_t)G, n_rows, row_ptr.data(), grp.data(), cnt.data(), B, mult.data(), counts.data(),
+                           local ? weights.data() : nullptr, scale, u_ref.data(), tot_ref.data(), group_counts.data(),
+                           a.precision, a.max_em_iterations, percent.data(), iterations.data()),
+       "refining the replicates");
+    std::vector<uint8_t> used(B + 1, 0);
+    uint32_t stopped = 0;
+    for (uint32_t b = 0; b <= B; ++b) {
+        used[b] = counts[(size_t)b * (G + 2)] != 0;
+        if (b && used[b] && iterations[b] >= a.max_em_iterations) ++stopped;
+    }
+    if (stopped)
+        std::cerr << "speq: the EM of " << stopped << " of " << B
+                  << " bootstrap replicates ran --max-em-iterations steps\n";
+    ok(speq_bootstrap_summary_percent(percent.data(), refined.data(), used.data(), B, (uint32_t)G, a.bootstrap_level,
+                                      ci.data()),
+       "summarising the bootstrap");
+    write_table(a.out_file_bootstrap_em, names, ci);
 }
 
 int run_scan(CmdArguments& a) {
@@ -842,7 +895,6 @@ int run_scan(CmdArguments& a) {
             std::cerr << speq::format_vector(percent) << "\n" << speq::format_vector(next) << "\n\n";
         }
     }
-    speq_em_free(em);
     phase("EM iterations");
 
     // The reference writes nothing to -o (quirk B1); we write the (refined) percentage vector there.
@@ -864,13 +916,15 @@ int run_scan(CmdArguments& a) {
         write_marker_coverage(a, d, prm, h.names);
         phase("marker coverage");
     }
-    // --bootstrap: one more pass over the same reads, placed like --group-sets; mode, pairing, k, cutoff and the fixed
-    // accuracy are the run's own. The intervals bound the initial percentages (the first vector printed above), not the
-    // EM-refined ones: those would need one histogram per replicate.
-    if (!a.out_file_bootstrap.empty()) {
-        write_bootstrap(a, d, prm, h.names, u_ref, tot_ref);
+    // --bootstrap / --bootstrap-em: one more pass over the same reads, placed like --group-sets; mode, pairing, k,
+    // cutoff and the fixed accuracy are the run's own. --bootstrap's intervals bound the initial percentages (the first
+    // vector printed above), --bootstrap-em's the EM-refined ones: the pass then fills one histogram per replicate
+    // through the run's finalized histogram, which is kept until here for it.
+    if (!a.out_file_bootstrap.empty() || !a.out_file_bootstrap_em.empty()) {
+        write_bootstrap(a, d, prm, h.names, u_ref, tot_ref, em, h.counts, percent);
         phase("bootstrap");
     }
+    speq_em_free(em);
     // The device replica, its pinned pipeline slots and the index are left to process exit: unpinning and freeing
     // them explicitly costs ~0.07 s and the process ends right after this.
     (void)d;

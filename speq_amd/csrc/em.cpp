@@ -154,8 +154,9 @@ void merge_equal_rows(speq_em& em) {
     mult.reserve(distinct);
     ptr.reserve(distinct + 1);
     for (uint64_t r = 0; r < R; ++r) {
-        if (rep[r] != r) {
+        if (rep[r] != r) {  // (rep[r] < r: a content's representative is its first row)
             mult[at[rep[r]]] += em.row_mult[r];
+            at[r] = at[rep[r]];
             continue;
         }
         at[r] = mult.size();
@@ -168,6 +169,7 @@ void merge_equal_rows(speq_em& em) {
     em.row_ptr.swap(ptr);
     em.col_group.swap(grp);
     em.col_count.swap(cnt);
+    for (uint32_t& r : em.iv_row) r = (uint32_t)at[r];
 }
 
 void em_build_rows(speq_em& em, const uint32_t* lo, const uint32_t* mult, const uint32_t* hi, uint64_t m) {
@@ -243,6 +245,9 @@ void em_build_rows(speq_em& em, const uint32_t* lo, const uint32_t* mult, const 
     }
     em.n_intervals = em.row_mult.size();
     em.n_entries = em.col_group.size();
+    em.iv_lo.assign(lo, lo + m);
+    em.iv_row.resize(m);
+    for (uint64_t r = 0; r < m; ++r) em.iv_row[r] = (uint32_t)r;  // (m is a u32 count: speq_em_finalize)
     merge_equal_rows(em);
     char msg[96];
     std::snprintf(msg, sizeof msg, "em rows: %llu intervals -> %llu rows",
@@ -281,85 +286,200 @@ int speq_em_rows(const speq_em* em, uint64_t* n_rows, uint64_t* n_entries, uint6
     });
 }
 
-// One EM step (fm_scanner.cpp:1098-1120 global, :1186-1214 local): for every passing window with hits,
-// a_i = c_i p_i / n_i, norm = sum_i a_i (group order), and if norm > 0, next_i += a_i / norm.
+
+int speq_em_intervals(const speq_em* em, uint64_t* n, uint32_t* lo, uint32_t* row) {
+    return speq::guarded([&] {
+        if (!em || !em->finalized) throw std::invalid_argument("speq_em_intervals: histogram not finalized");
+        if (n) *n = em->iv_lo.size();
+        if (lo) std::copy(em->iv_lo.begin(), em->iv_lo.end(), lo);
+        if (row) std::copy(em->iv_row.begin(), em->iv_row.end(), row);
+    });
+}
+
+}  // extern "C"
+
+namespace {
+
+// CSR rows as speq_em_rows returns them
+struct RowsView {
+    uint32_t G;
+    uint64_t R;
+    const uint64_t* ptr;
+    const uint32_t* grp;
+    const uint32_t* cnt;
+};
+
+// One EM step (fm_scanner.cpp:1098-1120 global, :1186-1214 local) over the rows with the multiplicities `mult`: for
+// every passing window with hits, a_i = c_i p_i / n_i, norm = sum_i a_i (group order), and if norm > 0,
+// next_i += a_i / norm. pooled: the chunks run on the step pool; otherwise on the caller, in chunk order. Either way
+// every chunk is summed by itself and the chunks are added in chunk order, so the result is the same bits.
+void em_sweep(const RowsView& T, const uint64_t* mult, const double* percent, const int32_t* group_counts,
+              const uint64_t* unique, double* next, bool pooled) {
+    const uint32_t G = T.G;
+    bool clean = true;  // every "0 * p_i / n_i" term is exactly 0 (no n_i == 0, finite p_i)
+    for (uint32_t g = 0; g < G; ++g) {
+        const double z = 0.0 * percent[g] / (double)group_counts[g];
+        if (!(z == 0.0)) clean = false;
+    }
+    std::fill(next, next + G, 0.0);
+    const uint64_t R = T.R;
+    if (clean) {
+        // single-group windows: a / a = 1 when a = c p_g / n_g > 0 (c >= 1), else norm == 0 and they are skipped
+        for (uint32_t g = 0; g < G; ++g) {
+            const double a = percent[g] / (double)group_counts[g];
+            if (a > 0.0) next[g] += (double)unique[g];
+        }
+        // Rows are split into a FIXED number of contiguous chunks (independent of the machine's thread count),
+        // each summed into its own vector, and the chunk vectors are added in chunk order: the result is
+        // deterministic, and differs from a serial sweep only by fp64 re-association (tests: rtol 1e-9).
+        const uint64_t n_chunks = std::min<uint64_t>(EM_CHUNKS, std::max<uint64_t>(1, T.ptr[R] / 16384));
+        std::vector<double> part(n_chunks * G, 0.0);
+        auto run_chunk = [&](uint64_t ci) {
+            const uint64_t r0 = R * ci / n_chunks, r1 = R * (ci + 1) / n_chunks;
+            double* acc = part.data() + ci * G;
+            std::vector<double> a;
+            for (uint64_t r = r0; r < r1; ++r) {
+                const uint64_t b = T.ptr[r], e = T.ptr[r + 1];
+                a.resize(e - b);
+                double norm = 0.0;
+                for (uint64_t x = b; x < e; ++x) {
+                    const uint32_t g = T.grp[x];
+                    a[x - b] = (double)T.cnt[x] * percent[g] / (double)group_counts[g];
+                    norm += a[x - b];
+                }
+                if (norm > 0.0) {
+                    const double m = (double)mult[r];
+                    for (uint64_t x = b; x < e; ++x) acc[T.grp[x]] += m * (a[x - b] / norm);
+                }
+            }
+        };
+        if (n_chunks <= 1 || !pooled) {
+            for (uint64_t ci = 0; ci < n_chunks; ++ci) run_chunk(ci);
+        } else {
+            step_pool().run(n_chunks, run_chunk);
+        }
+        for (uint64_t ci = 0; ci < n_chunks; ++ci)
+            for (uint32_t g = 0; g < G; ++g) next[g] += part[ci * G + g];
+    } else {
+        // IEEE edge cases (a group count of 0, non-finite percentages): evaluate every group of every row
+        // exactly as the reference does, zero terms included.
+        std::vector<double> a(G);
+        auto window = [&](const uint32_t* grp, const uint32_t* cnt, uint64_t nnz, double m) {
+            std::vector<double> h(G, 0.0);
+            for (uint64_t x = 0; x < nnz; ++x) h[grp[x]] = (double)cnt[x];
+            double norm = 0.0;
+            for (uint32_t g = 0; g < G; ++g) {
+                a[g] = h[g] * percent[g] / (double)group_counts[g];
+                norm += a[g];
+            }
+            if (norm > 0.0)
+                for (uint32_t g = 0; g < G; ++g) next[g] += m * (a[g] / norm);
+        };
+        for (uint32_t g = 0; g < G; ++g) {
+            if (!unique[g]) continue;
+            const uint32_t one = 1;
+            window(&g, &one, 1, (double)unique[g]);
+        }
+        for (uint64_t r = 0; r < R; ++r) {
+            const uint64_t b = T.ptr[r];
+            window(T.grp + b, T.cnt + b, T.ptr[r + 1] - b, (double)mult[r]);
+        }
+    }
+}
+
+// the rows a caller hands in: ascending row_ptr from 0, every group below G
+RowsView checked_rows(const char* who, uint32_t G, uint64_t n_rows, const uint64_t* row_ptr, const uint32_t* col_group,
+                      const uint32_t* col_count) {
+    if (!row_ptr) throw std::invalid_argument(std::string(who) + ": null row_ptr");
+    if (row_ptr[0] != 0) throw std::invalid_argument(std::string(who) + ": row_ptr[0] must be 0");
+    for (uint64_t r = 0; r < n_rows; ++r)
+        if (row_ptr[r + 1] < row_ptr[r]) throw std::invalid_argument(std::string(who) + ": row_ptr must ascend");
+    const uint64_t ne = row_ptr[n_rows];
+    if (ne && (!col_group || !col_count)) throw std::invalid_argument(std::string(who) + ": null entries");
+    for (uint64_t x = 0; x < ne; ++x)
+        if (col_group[x] >= G) throw std::invalid_argument(std::string(who) + ": a group index is not below G");
+    return RowsView{G, n_rows, row_ptr, col_group, col_count};
+}
+
+// unique_to_percent (fm_scanner.cpp:1455-1474)
+void unique_to_percent(uint32_t G, const double* ur, uint64_t total, const double* uref, const double* tref, double* out) {
+    for (uint32_t g = 0; g < G; ++g) {
+        out[g] = 0.0;
+        if (tref[g] > 0.0) {
+            const double pu = uref[g] / tref[g];
+            out[g] = 100.0 * ur[g] / static_cast<double>(total) / pu;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
 int speq_em_step(const speq_em* em, const double* percent, const int32_t* group_counts, const uint64_t* unique,
                  double* next) {
     return speq::guarded([&] {
         if (!em || !percent || !group_counts || !unique || !next) throw std::invalid_argument("speq_em_step: null argument");
         if (!em->finalized) throw std::invalid_argument("speq_em_step: histogram not finalized");
-        const uint32_t G = em->G;
-        std::vector<double> coef(G);  // p_i / n_i, evaluated as (c * p) / n below
-        bool clean = true;            // every "0 * p_i / n_i" term is exactly 0 (no n_i == 0, finite p_i)
-        for (uint32_t g = 0; g < G; ++g) {
-            const double z = 0.0 * percent[g] / (double)group_counts[g];
-            if (!(z == 0.0)) clean = false;
-        }
-        std::fill(next, next + G, 0.0);
-        const uint64_t R = em->row_mult.size();
-        if (clean) {
-            // single-group windows: a / a = 1 when a = c p_g / n_g > 0 (c >= 1), else norm == 0 and they are skipped
-            for (uint32_t g = 0; g < G; ++g) {
-                const double a = percent[g] / (double)group_counts[g];
-                if (a > 0.0) next[g] += (double)unique[g];
-            }
-            // Rows are split into a FIXED number of contiguous chunks (independent of the machine's thread count),
-            // each summed into its own vector, and the chunk vectors are added in chunk order: the result is
-            // deterministic, and differs from a serial sweep only by fp64 re-association (tests: rtol 1e-9).
-            const uint64_t n_chunks = std::min<uint64_t>(EM_CHUNKS, std::max<uint64_t>(1, em->col_group.size() / 16384));
-            std::vector<double> part(n_chunks * G, 0.0);
-            auto run_chunk = [&](uint64_t ci) {
-                const uint64_t r0 = R * ci / n_chunks, r1 = R * (ci + 1) / n_chunks;
-                double* acc = part.data() + ci * G;
-                std::vector<double> a;
-                for (uint64_t r = r0; r < r1; ++r) {
-                    const uint64_t b = em->row_ptr[r], e = em->row_ptr[r + 1];
-                    a.resize(e - b);
-                    double norm = 0.0;
-                    for (uint64_t x = b; x < e; ++x) {
-                        const uint32_t g = em->col_group[x];
-                        a[x - b] = (double)em->col_count[x] * percent[g] / (double)group_counts[g];
-                        norm += a[x - b];
-                    }
-                    if (norm > 0.0) {
-                        const double m = (double)em->row_mult[r];
-                        for (uint64_t x = b; x < e; ++x) acc[em->col_group[x]] += m * (a[x - b] / norm);
-                    }
+        const RowsView T{em->G, em->row_mult.size(), em->row_ptr.data(), em->col_group.data(), em->col_count.data()};
+        em_sweep(T, em->row_mult.data(), percent, group_counts, unique, next, true);
+    });
+}
+
+int speq_em_rows_step(uint32_t n_groups, uint64_t n_rows, const uint64_t* row_ptr, const uint32_t* col_group,
+                      const uint32_t* col_count, const uint64_t* mult, const double* percent,
+                      const int32_t* group_counts, const uint64_t* unique, double* next) {
+    return speq::guarded([&] {
+        const char* who = "speq_em_rows_step";
+        if ((n_rows && !mult) || (n_groups && (!percent || !group_counts || !unique || !next)))
+            throw std::invalid_argument(std::string(who) + ": null argument");
+        const RowsView T = checked_rows(who, n_groups, n_rows, row_ptr, col_group, col_count);
+        em_sweep(T, mult, percent, group_counts, unique, next, true);
+    });
+}
+
+int speq_em_rows_refine(uint32_t n_groups, uint64_t n_rows, const uint64_t* row_ptr, const uint32_t* col_group,
+                        const uint32_t* col_count, uint32_t replicates, const uint64_t* mult, const uint64_t* counts,
+                        const double* weights, double unique_scale, const uint64_t* u_ref, const uint64_t* tot_ref,
+                        const int32_t* group_counts, double precision, uint32_t max_iterations, double* percent_out,
+                        uint32_t* iterations_out) {
+    return speq::guarded([&] {
+        const char* who = "speq_em_rows_refine";
+        const uint32_t G = n_groups;
+        if ((n_rows && !mult) || !counts || !iterations_out || (G && (!u_ref || !tot_ref || !group_counts || !percent_out)))
+            throw std::invalid_argument(std::string(who) + ": null argument");
+        const RowsView T = checked_rows(who, G, n_rows, row_ptr, col_group, col_count);
+        std::vector<double> uref(u_ref, u_ref + G), tref(tot_ref, tot_ref + G);
+        std::atomic<bool> failed{false};
+        // the CLI's loop (speq_main.cpp) for one row of the matrices
+        auto one = [&](uint64_t b) {
+            try {
+                const uint64_t* c = counts + b * ((uint64_t)G + 2u);
+                double* percent = percent_out + b * G;
+                iterations_out[b] = 0;
+                std::fill(percent, percent + G, 0.0);
+                const uint64_t total = c[0];
+                if (total == 0 || G == 0) return;
+                std::vector<double> ut(G), next(G), np(G), diff(G, 1.0);
+                for (uint32_t g = 0; g < G; ++g)
+                    ut[g] = weights ? weights[b * G + g] : (double)c[2u + g] * unique_scale;
+                unique_to_percent(G, ut.data(), total, uref.data(), tref.data(), percent);
+                uint32_t it = 0;
+                while (*std::max_element(diff.begin(), diff.end()) > precision && it < max_iterations) {
+                    em_sweep(T, mult + b * n_rows, percent, group_counts, c + 2, next.data(), false);
+                    unique_to_percent(G, ut.data(), total, ut.data(), next.data(), np.data());
+                    for (uint32_t g = 0; g < G; ++g) diff[g] = std::fabs(np[g] - percent[g]);
+                    std::copy(np.begin(), np.end(), percent);
+                    ++it;
                 }
-            };
-            if (n_chunks <= 1) {
-                run_chunk(0);
-            } else {
-                step_pool().run(n_chunks, run_chunk);
+                iterations_out[b] = it;
+            } catch (...) {
+                failed = true;
             }
-            for (uint64_t ci = 0; ci < n_chunks; ++ci)
-                for (uint32_t g = 0; g < G; ++g) next[g] += part[ci * G + g];
-        } else {
-            // IEEE edge cases (a group count of 0, non-finite percentages): evaluate every group of every row
-            // exactly as the reference does, zero terms included.
-            std::vector<double> a(G);
-            auto window = [&](const uint32_t* grp, const uint32_t* cnt, uint64_t nnz, double m) {
-                std::vector<double> h(G, 0.0);
-                for (uint64_t x = 0; x < nnz; ++x) h[grp[x]] = (double)cnt[x];
-                double norm = 0.0;
-                for (uint32_t g = 0; g < G; ++g) {
-                    a[g] = h[g] * percent[g] / (double)group_counts[g];
-                    norm += a[g];
-                }
-                if (norm > 0.0)
-                    for (uint32_t g = 0; g < G; ++g) next[g] += m * (a[g] / norm);
-            };
-            for (uint32_t g = 0; g < G; ++g) {
-                if (!unique[g]) continue;
-                const uint32_t one = 1;
-                window(&g, &one, 1, (double)unique[g]);
-            }
-            for (uint64_t r = 0; r < R; ++r) {
-                const uint64_t b = em->row_ptr[r];
-                window(em->col_group.data() + b, em->col_count.data() + b, em->row_ptr[r + 1] - b,
-                       (double)em->row_mult[r]);
-            }
-        }
+        };
+        // replicates side by side on the step pool (at most 16 threads), each one's sweeps on its own thread
+        step_pool().run((uint64_t)replicates + 1u, one);
+        if (failed) throw std::runtime_error(std::string(who) + ": a replicate's refinement failed");
     });
 }
 

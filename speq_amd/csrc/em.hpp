@@ -30,6 +30,10 @@ struct speq_em {
     std::vector<uint64_t> row_ptr;
     std::vector<uint32_t> col_group;
     std::vector<uint32_t> col_count;
+    // the interval -> row map (speq_em_intervals): the ascending interval starts, and for each the index of the row
+    // above that it was merged into
+    std::vector<uint32_t> iv_lo;
+    std::vector<uint32_t> iv_row;
 };
 
 namespace speq {

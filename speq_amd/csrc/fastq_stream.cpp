@@ -1598,13 +1598,15 @@ extern "C" int speq_markers_fastq(speq_device_index* d, const char* path1, const
     return rc;
 }
 
-extern "C" int speq_bootstrap_fastq(speq_device_index* d, const char* path1, const char* path2,
-                                    const speq_scan_params* params, uint32_t replicates, uint64_t seed,
-                                    uint32_t threads, uint64_t* counts, double* weights, speq_stream_stats* stats) {
+// speq_bootstrap_fastq, and with em != NULL speq_bootstrap_em_fastq: the same stream into a handle with the histogram
+// attached
+static int bootstrap_fastq_impl(const char* who, speq_device_index* d, const speq_em* em, const char* path1,
+                                const char* path2, const speq_scan_params* params, uint32_t replicates, uint64_t seed,
+                                uint32_t threads, uint64_t* counts, double* weights, uint64_t* mult, uint64_t* missed,
+                                speq_stream_stats* stats) {
     const auto t0 = std::chrono::steady_clock::now();
     speq_scan_params p{};
     int rc = speq::guarded([&] {
-        const char* who = "speq_bootstrap_fastq";
         if (!params) throw std::invalid_argument(std::string(who) + ": null params");
         speq::check_report_k(who, params->k);
         if (replicates < 1 || replicates > SPEQ_BOOTSTRAP_MAX_REPLICATES)
@@ -1619,14 +1621,35 @@ extern "C" int speq_bootstrap_fastq(speq_device_index* d, const char* path1, con
     speq_bootstrap* b = nullptr;
     rc = speq_bootstrap_create(d, &p, replicates, seed, &b);  // (its own status: SPEQ_E_NOMEM)
     if (rc != SPEQ_OK) return rc;
-    rc = speq::guarded([&] {
-        BootstrapSink sink(b, p.paired != 0);
-        const StreamTotals tot = run_stream(path1, path2, threads, sink, false, false);
-        check_rc(speq_bootstrap_finalize(b, counts, p.mode == SPEQ_MODE_LOCAL ? weights : nullptr));
-        fill_stats(stats, tot, t0);
-    });
+    if (em) rc = speq_bootstrap_attach_em(b, em);
+    if (rc == SPEQ_OK)
+        rc = speq::guarded([&] {
+            BootstrapSink sink(b, p.paired != 0);
+            const StreamTotals tot = run_stream(path1, path2, threads, sink, false, false);
+            check_rc(speq_bootstrap_finalize(b, counts, p.mode == SPEQ_MODE_LOCAL ? weights : nullptr));
+            if (em) check_rc(speq_bootstrap_finalize_em(b, mult, missed));
+            fill_stats(stats, tot, t0);
+        });
     speq_bootstrap_free(b);
     return rc;
+}
+
+extern "C" int speq_bootstrap_fastq(speq_device_index* d, const char* path1, const char* path2,
+                                    const speq_scan_params* params, uint32_t replicates, uint64_t seed,
+                                    uint32_t threads, uint64_t* counts, double* weights, speq_stream_stats* stats) {
+    return bootstrap_fastq_impl("speq_bootstrap_fastq", d, nullptr, path1, path2, params, replicates, seed, threads,
+                                counts, weights, nullptr, nullptr, stats);
+}
+
+extern "C" int speq_bootstrap_em_fastq(speq_device_index* d, const speq_em* em, const char* path1, const char* path2,
+                                       const speq_scan_params* params, uint32_t replicates, uint64_t seed,
+                                       uint32_t threads, uint64_t* counts, double* weights, uint64_t* mult,
+                                       uint64_t* missed, speq_stream_stats* stats) {
+    if (!em) {
+        return speq::guarded([] { throw std::invalid_argument("speq_bootstrap_em_fastq: null histogram"); });
+    }
+    return bootstrap_fastq_impl("speq_bootstrap_em_fastq", d, em, path1, path2, params, replicates, seed, threads,
+                                counts, weights, mult, missed, stats);
 }
 
 extern "C" uint64_t speq_group_sets_count(const speq_group_sets* s) { return s ? s->units.size() : 0; }

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "em.hpp"
 #include "window_pass.hpp"
 
 struct speq_bootstrap {
@@ -30,6 +31,16 @@ struct speq_bootstrap {
     double* d_weights = nullptr;  // local mode only
     std::atomic<uint32_t> lds_path{0};
     std::atomic<uint64_t> units_added{0};
+    // an attached EM histogram (speq_bootstrap_attach_em): the sorted interval starts with the slot of
+    // each one's merged row, and M, u64 [n_rows][R], cell (slot, b) at slot * R + b
+    bool em_attached = false;
+    uint64_t em_rows = 0;
+    uint32_t em_m = 0, em_lds_rows = 0;
+    uint32_t* d_em_lo = nullptr;
+    uint32_t* d_em_slot = nullptr;
+    unsigned long long* d_em_mult = nullptr;
+    unsigned long long* d_em_missed = nullptr;
+    std::vector<uint32_t> em_slot_of_row;
 };
 
 namespace {
@@ -79,6 +90,22 @@ inline bool fits_lds(uint32_t R, uint32_t G, bool local, uint32_t k) {
     return acc_bytes(R, G, local) + (uint64_t)WAVES_PER_BLOCK * wave_bytes(k) <= LDS_BUDGET;
 }
 
+// What a launch with an attached histogram takes beside the counters: lo[m] ascending, slot[m], the first `lds_rows`
+// slots' cells in the block's LDS and every other slot's in mult
+struct EmDev {
+    const uint32_t* lo;
+    const uint32_t* slot;
+    unsigned long long* mult;
+    unsigned long long* missed;
+    uint32_t m, lds_rows;
+};
+// rows of an attached histogram whose R cells a block keeps in LDS: what is left of LDS_BUDGET after the tile search's
+// regions and, when they take the LDS path, the counters
+inline uint32_t em_lds_rows(uint64_t n_rows, uint32_t R, uint32_t G, bool local, uint32_t k) {
+    const uint64_t taken = (uint64_t)WAVES_PER_BLOCK * wave_bytes(k) + (fits_lds(R, G, local, k) ? acc_bytes(R, G, local) : 0u);
+    return (uint32_t)std::min<uint64_t>(n_rows, taken >= LDS_BUDGET ? 0u : (LDS_BUDGET - taken) / (8ull * R));
+}
+
 // sum over the wave of v (every lane gets it)
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -92,12 +119,17 @@ __device__ __forceinline__ double wave_sum(double v) {
 // and after the unit's tiles w_b * passing to cell (0, b) and, for a unit with two or more groups, w_b to cell (1, b).
 // The weights are recomputed where they are used (two 64-bit multiplies and a few compares). LOCAL: a lane also has
 // its window's Phred weight x (the scan's chain of divisions), and the round adds w_b * (sum of x over the group's
-// windows of the tile) to the weights cell (g, b).
-template <bool PAIRED, bool LOCAL, bool LDS_ACC>
+// windows of the tile) to the weights cell (g, b). EM (an attached histogram): a lane whose window lies in two or more
+// groups looks its interval start up in E.lo (binary search; the table is L2-resident) and takes the slot of its merged
+// row, and one more wave-uniform loop, a round per distinct slot of the tile, adds w_b * (windows of the tile in the
+// slot) to cell (slot, b): in the block's LDS for the slots below E.lds_rows, which are flushed with the counters, and
+// in E.mult for the rest. A start that the table does not hold is counted in *E.missed, once per tile.
+template <bool PAIRED, bool LOCAL, bool LDS_ACC, bool EM>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_read_bootstrap(
     const DevView I, const uint8_t* __restrict__ seq, const uint8_t* __restrict__ qual, const uint64_t* __restrict__ off,
     uint64_t n_units, uint64_t first_unit, uint32_t k, uint32_t cutoff, uint32_t R, uint64_t seed,
-    const double* __restrict__ qlut, unsigned long long* __restrict__ g_counts, double* __restrict__ g_weights) {
+    const double* __restrict__ qlut, unsigned long long* __restrict__ g_counts, double* __restrict__ g_weights,
+    const EmDev E) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint16_t* cnt = wave_cnt(lds, wave, k);
@@ -111,6 +143,13 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_read_bootstrap(
         wacc = reinterpret_cast<double*>(acc + n_cells);
         for (uint32_t i = threadIdx.x; i < n_cells; i += BLOCK_THREADS) acc[i] = 0ull;
         for (uint32_t i = threadIdx.x; i < n_wcells; i += BLOCK_THREADS) wacc[i] = 0.0;
+        __syncthreads();
+    }
+    unsigned long long* hot = nullptr;
+    if (EM) {
+        hot = reinterpret_cast<unsigned long long*>(lds + WAVES_PER_BLOCK * wave_bytes(k)) +
+              (LDS_ACC ? n_cells + n_wcells : 0u);
+        for (uint32_t i = threadIdx.x; i < E.lds_rows * R; i += BLOCK_THREADS) hot[i] = 0ull;
         __syncthreads();
     }
     const Rsrc Rs = make_rsrc(I);
@@ -130,6 +169,17 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_read_bootstrap(
                 bool pass;
                 int res = search_tile(I, Rs, sym, cnt, span, k, tile + lane < nwin, lane, lo,
                                       SPEQ_READ_TILE_AT(seq, qual, beg + tile, cutoff), &pass);
+                constexpr uint32_t NO_SLOT = 0xFFFFFFFFu, MISSED = 0xFFFFFFFEu;
+                uint32_t slot = NO_SLOT;
+                if (EM && res == -2) {
+                    uint32_t a = 0, e = E.m;
+                    while (a < e) {
+                        const uint32_t mid = (a + e) >> 1;
+                        if (E.lo[mid] < lo) a = mid + 1u;
+                        else e = mid;
+                    }
+                    slot = a < E.m && E.lo[a] == lo ? E.slot[a] : MISSED;
+                }
                 if ((uint32_t)res >= G) res = -1;  // (also every negative result)
                 passing += (uint32_t)__popcll(__ballot(pass));
                 double x = 0.0;
@@ -158,6 +208,23 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_read_bootstrap(
                         if (LOCAL) atomicAdd(&wacc[(uint32_t)g * R + b], (double)w * x_g);
                     }
                 }
+                if (EM) {
+                    const uint64_t miss = __ballot(slot == MISSED);
+                    if (miss != 0ull && lane == 0u) atomicAdd(E.missed, (unsigned long long)__popcll(miss));
+                    uint64_t left = __ballot(slot < MISSED);  // wave-uniform: one round per distinct slot of the tile
+                    while (left != 0ull) {
+                        const uint32_t s = (uint32_t)__shfl((int)slot, __builtin_ctzll(left));
+                        const uint64_t of_s = __ballot(slot == s);
+                        left &= ~of_s;
+                        const uint32_t n_s = (uint32_t)__popcll(of_s);
+                        unsigned long long* cell = s < E.lds_rows ? hot + s * R : E.mult + (uint64_t)s * R;
+                        for (uint32_t b = lane; b < R; b += 64u) {
+                            const uint32_t w = rep_weight(key, b);
+                            if (w == 0u) continue;
+                            atomicAdd(&cell[b], (unsigned long long)w * n_s);
+                        }
+                    }
+                }
             }
         }
         if (passing != 0u)
@@ -175,15 +242,23 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_read_bootstrap(
         for (uint32_t i = threadIdx.x; i < n_wcells; i += BLOCK_THREADS)
             if (wacc[i] != 0.0) atomicAdd(&g_weights[i], wacc[i]);
     }
+    if (EM) {
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < E.lds_rows * R; i += BLOCK_THREADS)
+            if (hot[i] != 0ull) atomicAdd(&E.mult[i], hot[i]);
+    }
 }
 
 using Kernel = void (*)(const DevView, const uint8_t*, const uint8_t*, const uint64_t*, uint64_t, uint64_t, uint32_t,
-                        uint32_t, uint32_t, uint64_t, const double*, unsigned long long*, double*);
+                        uint32_t, uint32_t, uint64_t, const double*, unsigned long long*, double*, const EmDev);
 template <bool PAIRED, bool LOCAL>
-Kernel pick(bool lds) { return lds ? k_read_bootstrap<PAIRED, LOCAL, true> : k_read_bootstrap<PAIRED, LOCAL, false>; }
-Kernel pick(bool paired, bool local, bool lds) {
-    if (paired) return local ? pick<true, true>(lds) : pick<true, false>(lds);
-    return local ? pick<false, true>(lds) : pick<false, false>(lds);
+Kernel pick(bool lds, bool em) {
+    if (em) return lds ? k_read_bootstrap<PAIRED, LOCAL, true, true> : k_read_bootstrap<PAIRED, LOCAL, false, true>;
+    return lds ? k_read_bootstrap<PAIRED, LOCAL, true, false> : k_read_bootstrap<PAIRED, LOCAL, false, false>;
+}
+Kernel pick(bool paired, bool local, bool lds, bool em) {
+    if (paired) return local ? pick<true, true>(lds, em) : pick<true, false>(lds, em);
+    return local ? pick<false, true>(lds, em) : pick<false, false>(lds, em);
 }
 
 // guarded() with the device allocations' failure as SPEQ_E_NOMEM (as speq_markers_*)
@@ -256,15 +331,18 @@ void add_device_impl(speq_bootstrap* b, const uint8_t* d_seq, const uint8_t* d_q
     const uint32_t k = b->params.k, R = b->B + 1u;
     const bool local = is_local(b->params), lds_acc = fits_lds(R, b->G, local, k);
     const DevView v = speq::search_view(d, k);
-    const size_t lds = (size_t)WAVES_PER_BLOCK * wave_bytes(k) + (lds_acc ? (size_t)acc_bytes(R, b->G, local) : 0);
-    // LDS path: a block zeroes and flushes its accumulators once, so the grid is a few blocks per CU and the waves
-    // stride over the units; global path: as the report's
+    const EmDev E{b->d_em_lo, b->d_em_slot, b->d_em_mult, b->d_em_missed, b->em_m, b->em_lds_rows};
+    const size_t lds = (size_t)WAVES_PER_BLOCK * wave_bytes(k) + (lds_acc ? (size_t)acc_bytes(R, b->G, local) : 0) +
+                       (size_t)E.lds_rows * R * 8u;
+    // LDS path (the counters', or an attached histogram's hot rows alone): a block zeroes and flushes its accumulators
+    // once, so the grid is a few blocks per CU and the waves stride over the units; global path: as the report's
+    const bool lds_grid = lds_acc || E.lds_rows != 0u;
     const uint64_t want = (n_units + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     const uint64_t per_cu = std::min<uint64_t>(std::max<uint64_t>((160u << 10) / lds, 2), 8);  // resident blocks
-    const uint64_t blocks = std::min<uint64_t>(want, lds_acc ? per_cu * std::max(d->n_cus, 1u) : 16384u);
-    hipLaunchKernelGGL(pick(paired, local, lds_acc), dim3((uint32_t)blocks), dim3(BLOCK_THREADS), lds, st, v, d_seq,
-                       d_qual, d_offsets, n_units, first_unit, k, b->params.phred_cutoff, R, b->seed, d->d_qlut,
-                       b->d_counts, b->d_weights);
+    const uint64_t blocks = std::min<uint64_t>(want, lds_grid ? per_cu * std::max(d->n_cus, 1u) : 16384u);
+    hipLaunchKernelGGL(pick(paired, local, lds_acc, b->em_attached), dim3((uint32_t)blocks), dim3(BLOCK_THREADS), lds,
+                       st, v, d_seq, d_qual, d_offsets, n_units, first_unit, k, b->params.phred_cutoff, R, b->seed,
+                       d->d_qlut, b->d_counts, b->d_weights, E);
     HIP_OK(hipGetLastError());
     b->lds_path = lds_acc ? 1u : 0u;
     b->units_added += n_units;
@@ -311,31 +389,92 @@ void finalize_impl(speq_bootstrap* b, uint64_t* counts, double* weights) {
     }
 }
 
+// ---- an attached EM histogram ----
+void free_em(speq_bootstrap* b) {
+    if (b->d_em_lo) (void)hipFree(b->d_em_lo);
+    if (b->d_em_slot) (void)hipFree(b->d_em_slot);
+    if (b->d_em_mult) (void)hipFree(b->d_em_mult);
+    if (b->d_em_missed) (void)hipFree(b->d_em_missed);
+    b->d_em_lo = b->d_em_slot = nullptr;
+    b->d_em_mult = b->d_em_missed = nullptr;
+}
+
+void attach_em_impl(speq_bootstrap* b, const speq_em* em) {
+    const char* who = "speq_bootstrap_attach_em";
+    if (!b || !em) throw std::invalid_argument(std::string(who) + ": null argument");
+    if (!em->finalized) throw std::invalid_argument(std::string(who) + ": histogram not finalized");
+    if (em->dev != b->dev || em->G != b->G)
+        throw std::invalid_argument(std::string(who) + ": the histogram is of another replica");
+    if (b->em_attached) throw std::invalid_argument(std::string(who) + ": a histogram is attached already");
+    if (b->units_added.load() != 0) throw std::invalid_argument(std::string(who) + ": reads have been added already");
+    speq_device_index* d = b->dev;
+    DeviceGuard g(d->device);
+    const uint64_t n_rows = em->row_mult.size(), m = em->iv_lo.size();
+    const uint32_t R = b->B + 1u;
+    // slots: the rows by descending multiplicity of the sample, ties by row index, so that the hot rows are the ones
+    // a block keeps in LDS
+    std::vector<uint32_t> order(n_rows);
+    for (uint64_t r = 0; r < n_rows; ++r) order[r] = (uint32_t)r;
+    std::stable_sort(order.begin(), order.end(),
+                     [&](uint32_t x, uint32_t y) { return em->row_mult[x] > em->row_mult[y]; });
+    std::vector<uint32_t> slot_of_row(n_rows), slot(m);
+    for (uint64_t s = 0; s < n_rows; ++s) slot_of_row[order[s]] = (uint32_t)s;
+    for (uint64_t i = 0; i < m; ++i) slot[i] = slot_of_row[em->iv_row[i]];
+    const size_t mb = (size_t)(n_rows * R * 8u);
+    try {
+        dev_alloc(reinterpret_cast<void**>(&b->d_em_lo), m * 4u, who);
+        dev_alloc(reinterpret_cast<void**>(&b->d_em_slot), m * 4u, who);
+        dev_alloc(reinterpret_cast<void**>(&b->d_em_mult), mb, who);
+        dev_alloc(reinterpret_cast<void**>(&b->d_em_missed), 8, who);
+        if (m) {
+            HIP_OK(hipMemcpyAsync(b->d_em_lo, em->iv_lo.data(), m * 4u, hipMemcpyHostToDevice, d->stream));
+            HIP_OK(hipMemcpyAsync(b->d_em_slot, slot.data(), m * 4u, hipMemcpyHostToDevice, d->stream));
+        }
+        HIP_OK(hipMemsetAsync(b->d_em_mult, 0, std::max<size_t>(mb, 16), d->stream));
+        HIP_OK(hipMemsetAsync(b->d_em_missed, 0, 8, d->stream));
+        HIP_OK(hipStreamSynchronize(d->stream));  // (the host vectors above are read until here)
+    } catch (...) {
+        (void)hipStreamSynchronize(d->stream);
+        free_em(b);
+        throw;
+    }
+    b->em_rows = n_rows;
+    b->em_m = (uint32_t)m;
+    b->em_lds_rows = em_lds_rows(n_rows, R, b->G, is_local(b->params), b->params.k);
+    b->em_slot_of_row.swap(slot_of_row);
+    b->em_attached = true;
+}
+
+void finalize_em_impl(speq_bootstrap* b, uint64_t* mult, uint64_t* missed) {
+    const char* who = "speq_bootstrap_finalize_em";
+    if (!b) throw std::invalid_argument(std::string(who) + ": null handle");
+    if (!b->em_attached) throw std::invalid_argument(std::string(who) + ": no histogram attached");
+    if (!mult && b->em_rows) throw std::invalid_argument(std::string(who) + ": null output");
+    speq_device_index* d = b->dev;
+    DeviceGuard g(d->device);
+    HIP_OK(hipDeviceSynchronize());  // the adds of every stream of the device have completed
+    const uint64_t R = b->B + 1u, n_rows = b->em_rows;
+    std::vector<uint64_t> hm((size_t)(n_rows * R));
+    if (n_rows) HIP_OK(hipMemcpy(hm.data(), b->d_em_mult, hm.size() * 8, hipMemcpyDeviceToHost));
+    for (uint64_t row = 0; row < n_rows; ++row) {
+        const uint64_t* cells = hm.data() + (uint64_t)b->em_slot_of_row[row] * R;
+        for (uint64_t r = 0; r < R; ++r) mult[r * n_rows + row] = cells[r];
+    }
+    if (missed) HIP_OK(hipMemcpy(missed, b->d_em_missed, 8, hipMemcpyDeviceToHost));
+}
+
 // ---- the summary (host only) ----
-void summary_impl(const uint64_t* counts, const double* weights, uint32_t replicates, uint32_t n_groups,
-                  const uint64_t* u_ref, const uint64_t* tot_ref, double unique_scale, double level,
-                  speq_bootstrap_ci* out) {
-    const char* who = "speq_bootstrap_summary";
-    if (!counts || !u_ref || !tot_ref || !out) throw std::invalid_argument(std::string(who) + ": null argument");
-    if (replicates < 1 || replicates > SPEQ_BOOTSTRAP_MAX_REPLICATES)
-        throw std::invalid_argument(std::string(who) + ": replicates must be in [1, " +
-                                    std::to_string(SPEQ_BOOTSTRAP_MAX_REPLICATES) + "]");
-    if (!(level > 0.0 && level < 1.0)) throw std::invalid_argument(std::string(who) + ": level must be in (0, 1)");
-    const uint32_t G = n_groups, C = G + 2u;
-    // unique_to_percent (fm_scanner.cpp:1455-1474) of row b
-    auto percent = [&](uint32_t b, uint32_t g) {
-        if (!((double)tot_ref[g] > 0.0)) return 0.0;
-        const double ur = weights ? weights[(size_t)b * G + g] : (double)counts[(size_t)b * C + 2u + g] * unique_scale;
-        const double pu = (double)u_ref[g] / (double)tot_ref[g];
-        return 100.0 * ur / (double)counts[(size_t)b * C] / pu;
-    };
+// The statistics of speq_bootstrap_summary over value(b, g), b = 1 .. B where used(b); estimate(g) is the sample's.
+template <class Value, class Used, class Estimate>
+void summarise(uint32_t replicates, uint32_t G, double level, Value&& value, Used&& used, Estimate&& estimate,
+               speq_bootstrap_ci* out) {
     std::vector<double> v;
     for (uint32_t g = 0; g < G; ++g) {
         speq_bootstrap_ci ci{};
-        ci.estimate = percent(0, g);
+        ci.estimate = estimate(g);
         v.clear();
         for (uint32_t b = 1; b <= replicates; ++b)
-            if (counts[(size_t)b * C] != 0) v.push_back(percent(b, g));
+            if (used(b)) v.push_back(value(b, g));
         const size_t n = v.size();
         ci.used = n;
         if (n) {
@@ -354,6 +493,44 @@ void summary_impl(const uint64_t* counts, const double* weights, uint32_t replic
         }
         out[g] = ci;
     }
+}
+
+void check_summary_args(const char* who, uint32_t replicates, double level) {
+    if (replicates < 1 || replicates > SPEQ_BOOTSTRAP_MAX_REPLICATES)
+        throw std::invalid_argument(std::string(who) + ": replicates must be in [1, " +
+                                    std::to_string(SPEQ_BOOTSTRAP_MAX_REPLICATES) + "]");
+    if (!(level > 0.0 && level < 1.0)) throw std::invalid_argument(std::string(who) + ": level must be in (0, 1)");
+}
+
+void summary_percent_impl(const double* percent, const double* estimate, const uint8_t* used_mask, uint32_t replicates,
+                          uint32_t n_groups, double level, speq_bootstrap_ci* out) {
+    const char* who = "speq_bootstrap_summary_percent";
+    if (!percent || !used_mask || !out) throw std::invalid_argument(std::string(who) + ": null argument");
+    check_summary_args(who, replicates, level);
+    const uint32_t G = n_groups;
+    summarise(
+        replicates, G, level, [&](uint32_t b, uint32_t g) { return percent[(size_t)b * G + g]; },
+        [&](uint32_t b) { return used_mask[b] != 0; }, [&](uint32_t g) { return estimate ? estimate[g] : percent[g]; },
+        out);
+}
+
+void summary_impl(const uint64_t* counts, const double* weights, uint32_t replicates, uint32_t n_groups,
+                  const uint64_t* u_ref, const uint64_t* tot_ref, double unique_scale, double level,
+                  speq_bootstrap_ci* out) {
+    const char* who = "speq_bootstrap_summary";
+    if (!counts || !u_ref || !tot_ref || !out) throw std::invalid_argument(std::string(who) + ": null argument");
+    check_summary_args(who, replicates, level);
+    const uint32_t G = n_groups, C = G + 2u;
+    // unique_to_percent (fm_scanner.cpp:1455-1474) of row b
+    auto percent = [&](uint32_t b, uint32_t g) {
+        if (!((double)tot_ref[g] > 0.0)) return 0.0;
+        const double ur = weights ? weights[(size_t)b * G + g] : (double)counts[(size_t)b * C + 2u + g] * unique_scale;
+        const double pu = (double)u_ref[g] / (double)tot_ref[g];
+        return 100.0 * ur / (double)counts[(size_t)b * C] / pu;
+    };
+    summarise(
+        replicates, G, level, percent, [&](uint32_t b) { return counts[(size_t)b * C] != 0; },
+        [&](uint32_t g) { return percent(0, g); }, out);
 }
 
 }  // namespace
@@ -395,7 +572,31 @@ void speq_bootstrap_free(speq_bootstrap* b) {
     if (!b) return;
     if (b->d_counts) (void)hipFree(b->d_counts);
     if (b->d_weights) (void)hipFree(b->d_weights);
+    free_em(b);
     delete b;
+}
+
+int speq_bootstrap_attach_em(speq_bootstrap* b, const speq_em* em) {
+    return guarded_nomem([&] { attach_em_impl(b, em); });
+}
+
+int speq_bootstrap_em_info(const speq_bootstrap* b, uint64_t* n_rows, uint32_t* lds_rows) {
+    return speq::guarded([&] {
+        if (!b) throw std::invalid_argument("speq_bootstrap_em_info: null handle");
+        if (!b->em_attached) throw std::invalid_argument("speq_bootstrap_em_info: no histogram attached");
+        if (n_rows) *n_rows = b->em_rows;
+        if (lds_rows) *lds_rows = b->em_lds_rows;
+    });
+}
+
+int speq_bootstrap_finalize_em(speq_bootstrap* b, uint64_t* mult, uint64_t* missed) {
+    return guarded_nomem([&] { finalize_em_impl(b, mult, missed); });
+}
+
+int speq_bootstrap_summary_percent(const double* percent, const double* estimate, const uint8_t* used_mask,
+                                   uint32_t replicates, uint32_t n_groups, double level, speq_bootstrap_ci* out) {
+    return speq::guarded(
+        [&] { summary_percent_impl(percent, estimate, used_mask, replicates, n_groups, level, out); });
 }
 
 uint32_t speq_bootstrap_weight(uint64_t seed, uint64_t unit, uint32_t replicate) {
