@@ -304,6 +304,64 @@ int speq_bootstrap_em_info(const speq_bootstrap* b, uint64_t* n_rows, uint32_t* 
  * (may be NULL) is 0. */
 int speq_bootstrap_finalize_em(speq_bootstrap* b, uint64_t* mult, uint64_t* missed);
 
+/* ---- duplicate reads: every distinct read (pair) counted once (a pass beside the scan) ----
+ * A unit is a record, or the pair of records (2i, 2i + 1) of a paired handle. Its fingerprint is (F_0, F_1),
+ *   F_s = sum over mates m in {0, 1} and positions i of that mate of mix(S_s + g (1 + c + 5 i + (m << 40)))  (mod 2^64),
+ *   c = the scan's dna5 code of the base (A C G T/U in either case 0..3, every other byte 4; qualities do not enter),
+ *   mix = splitmix64's finaliser, g = 0x9e3779b97f4a7c15, S_0 = 0x243f6a8885a308d3, S_1 = 0x13198a2e03707344;
+ * an empty unit has (0, 0); a record must be shorter than 2^32. Two units are duplicates iff their fingerprints are
+ * equal: that is the definition. Two distinct sequences collide with probability about 2^-128 per pair. Position and
+ * mate are inside the term, so a prefix, a shifted read and swapped mates differ. rep[u] is the lowest unit index of
+ * u's fingerprint, and u is kept iff rep[u] == u, whatever the batch cuts, streams or thread counts. The records of the
+ * other units get '!' (Phred 0) over their qualities: a window passes only if every quality is above the unsigned
+ * cutoff, so a scan of the masked reads equals, counter for counter, a scan of the reads with those units removed.
+ * The handle holds 20 bytes per unit on the replica's GPU (24 after a finalize), in chunks of 65,536 units allocated
+ * as the adds reach them; the replica must outlive it. Unit indices stay below 2^32 - 1. The reference keeps none of
+ * this. */
+#define SPEQ_DEDUP_BINS 8
+typedef struct {
+    uint64_t units;            /* N */
+    uint64_t distinct;         /* classes of equal fingerprint */
+    uint64_t max_multiplicity; /* units of the largest class */
+    uint64_t reserved;         /* 0 */
+    uint64_t mult_hist[SPEQ_DEDUP_BINS]; /* [j]: classes of exactly j + 1 units, j < 7; [7]: of 8 or more; sum = distinct */
+} speq_dedup_stats; /* 96 bytes */
+typedef struct speq_dedup speq_dedup;
+struct speq_em;
+int speq_dedup_create(speq_device_index* d, uint32_t paired, speq_dedup** out);
+/* Fingerprints n_reads records (an even number for a paired handle) whose first unit has index first_unit. Device
+ * buffers, asynchronous on stream; writes nothing but the handle's storage. Adds may come in any order, in any number of
+ * calls and on several streams. SPEQ_E_ARG when a unit index would reach 2^32 - 1, SPEQ_E_NOMEM when a chunk does not
+ * fit. n_reads == 0 launches nothing. */
+int speq_dedup_add_reads_device(speq_dedup* h, const uint8_t* d_seq, const uint64_t* d_offsets, uint64_t n_reads,
+                                uint64_t first_unit, void* stream);
+/* Host buffers, synchronous, staged in batches like speq_report_reads; first_unit counts units, not records. */
+int speq_dedup_add_reads(speq_dedup* h, const uint8_t* seq, const uint64_t* offsets, uint64_t n_reads,
+                         uint64_t first_unit);
+/* Waits for the device. The units added so far must be exactly 0 .. N - 1, each once: otherwise SPEQ_E_ARG, and the
+ * handle stays usable (add what is missing and finalize again). Sorts the fingerprints, marks the representatives and
+ * fills *out. More adds and another finalize cover everything added so far, like speq_markers_finalize. */
+int speq_dedup_finalize(speq_dedup* h, speq_dedup_stats* out);
+/* The three below need a finalize with no add after it and a unit range inside 0 .. N - 1; otherwise SPEQ_E_ARG. */
+/* Test accessor: rep[first_unit .. first_unit + n_units) to the host. */
+int speq_dedup_representatives(speq_dedup* h, uint64_t first_unit, uint64_t n_units, uint32_t* rep);
+/* Writes '!' over the quality bytes of every record of a unit that is not kept, and nothing else; d_offsets holds
+ * n_reads + 1 offsets, record r belongs to unit first_unit + r / (records per unit). Asynchronous on stream. */
+int speq_dedup_mask_device(speq_dedup* h, uint8_t* d_qual, const uint64_t* d_offsets, uint64_t n_reads,
+                           uint64_t first_unit, void* stream);
+/* The scan of host reads with the duplicates masked: staged in batches like speq_report_reads, the mask goes over the
+ * staged qualities (seq, qual and offsets are only read), then speq_em_scan_reads_device when em is given (a histogram
+ * of the handle's replica, not finalized) and speq_scan_reads_device otherwise. The batches' counters are ADDED to
+ * counts (u64 [G + 2]) and, in local mode, to weights (f64 [G]; NULL otherwise): the caller zeroes them. SPEQ_E_ARG
+ * also when params->paired differs from the handle's. Synchronous. */
+int speq_dedup_scan_reads(speq_dedup* h, struct speq_em* em, const uint8_t* seq, const uint8_t* qual,
+                          const uint64_t* offsets, uint64_t n_reads, uint64_t first_unit,
+                          const speq_scan_params* params, uint64_t* counts, double* weights);
+void speq_dedup_free(speq_dedup* h);
+/* Host only: the fingerprint of the unit (seq1, seq2) as the kernel computes it; seq2 NULL or len2 0 for a single-end
+ * unit (an empty mate 2 adds nothing). */
+void speq_dedup_fingerprint(const uint8_t* seq1, uint64_t len1, const uint8_t* seq2, uint64_t len2, uint64_t out[2]);
+
 /* ---- reference-uniqueness pass (replaces _async_count_unique_kmers_per_group, fm_scanner.cpp:1476-1576)
  * For every window of every text (fwd and rc of each record): Tot_ref[g] += 1, and U_ref[g] += 1 iff
  * every occurrence lies in a text of group g.  Outputs are host arrays of G u64 (overwritten). */
@@ -475,6 +533,16 @@ int speq_bootstrap_em_fastq(speq_device_index* d, const speq_em* em, const char*
                             const speq_scan_params* params, uint32_t replicates, uint64_t seed, uint32_t threads,
                             uint64_t* counts, double* weights, uint64_t* mult, uint64_t* missed,
                             speq_stream_stats* stats);
+
+/* The deduplicated scan (speq_dedup_*) of the whole of FASTQ file(s) (plain or gzip; paired when path2 != NULL) through
+ * a handle of its own, in two passes of the sequential reader with host-parsed blocks, each block carrying the index of
+ * its first record: pass 1 adds every block, one finalize fills *stats (may be NULL), pass 2 runs speq_dedup_scan_reads
+ * on every block. counts (u64 [G + 2]) and, in local mode, weights (f64 [G]; NULL otherwise) are overwritten with the
+ * totals; with em (may be NULL; not finalized) the scan also fills that histogram. The statistics and the counts do not
+ * depend on `threads`. st (may be NULL) describes pass 2. */
+int speq_dedup_fastq(speq_device_index* d, struct speq_em* em, const char* path1, const char* path2,
+                     const speq_scan_params* params, uint32_t threads, speq_dedup_stats* stats, uint64_t* counts,
+                     double* weights, speq_stream_stats* st);
 
 /* ---- several GPUs in one process ----
  * Reads shard across the GPUs of a node, the index is replicated (one speq_device_index per GPU, opened from the

@@ -70,6 +70,14 @@ class BootstrapCI(C.Structure):
                 ("hi", C.c_double), ("used", C.c_uint64)]
 
 
+DEDUP_BINS = 8
+
+
+class DedupStatsRecord(C.Structure):
+    _fields_ = [("units", C.c_uint64), ("distinct", C.c_uint64), ("max_multiplicity", C.c_uint64),
+                ("reserved", C.c_uint64), ("mult_hist", C.c_uint64 * DEDUP_BINS)]
+
+
 _U32P = C.POINTER(C.c_uint32)
 SIGNATURES = {
     "speq_last_error": (C.c_char_p, []),
@@ -126,6 +134,18 @@ SIGNATURES = {
     "speq_bootstrap_finalize_em": (C.c_int, [_P, _U64P, _U64P]),
     "speq_bootstrap_em_fastq": (C.c_int, [_P, _P, C.c_char_p, C.c_char_p, C.POINTER(ScanParams), C.c_uint32,
                                           C.c_uint64, C.c_uint32, _U64P, _F64P, _U64P, _U64P, C.POINTER(StreamStats)]),
+    "speq_dedup_create": (C.c_int, [_P, C.c_uint32, C.POINTER(_P)]),
+    "speq_dedup_add_reads_device": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, _P]),
+    "speq_dedup_add_reads": (C.c_int, [_P, C.c_char_p, _U64P, C.c_uint64, C.c_uint64]),
+    "speq_dedup_finalize": (C.c_int, [_P, C.POINTER(DedupStatsRecord)]),
+    "speq_dedup_representatives": (C.c_int, [_P, C.c_uint64, C.c_uint64, _U32P]),
+    "speq_dedup_mask_device": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, _P]),
+    "speq_dedup_scan_reads": (C.c_int, [_P, _P, C.c_char_p, C.c_char_p, _U64P, C.c_uint64, C.c_uint64,
+                                        C.POINTER(ScanParams), _U64P, _F64P]),
+    "speq_dedup_free": (None, [_P]),
+    "speq_dedup_fingerprint": (None, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, _U64P]),
+    "speq_dedup_fastq": (C.c_int, [_P, _P, C.c_char_p, C.c_char_p, C.POINTER(ScanParams), C.c_uint32,
+                                   C.POINTER(DedupStatsRecord), _U64P, _F64P, C.POINTER(StreamStats)]),
     "speq_ref_unique": (C.c_int, [_P, C.c_uint32, _U64P, _U64P]),
     "speq_ref_unique_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P]),
     "speq_comm_unique_id": (C.c_int, [_P]),

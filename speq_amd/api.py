@@ -21,9 +21,10 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._lib import (MARKER_BINS, SPEQ_MODE_GLOBAL, SPEQ_MODE_LOCAL, BootstrapCI, BuildOpts, IndexInfo,  # noqa: F401
-                   ScanParams, Slot, SpeqError, StreamStats, check, lib)
+                   DedupStatsRecord, ScanParams, Slot, SpeqError, StreamStats, check, lib)
 
-__all__ = ["FmIndex", "DeviceIndex", "Node", "Pipeline", "ScanResult", "ReadReport", "Markers", "MarkerCoverage", "Bootstrap", "bootstrap_summary", "bootstrap_summary_percent", "em_rows_step", "em_rows_refine", "Groupings", "EmHistogram", "Comm", "file_to_map", "unique_to_percent",
+__all__ = ["FmIndex", "DeviceIndex", "Node", "Pipeline", "ScanResult", "ReadReport", "Markers", "MarkerCoverage", "Bootstrap",
+           "Dedup", "DedupStats", "dedup_fingerprint", "bootstrap_summary", "bootstrap_summary_percent", "em_rows_step", "em_rows_refine", "Groupings", "EmHistogram", "Comm", "file_to_map", "unique_to_percent",
            "em_refine", "pack_records", "SpeqError", "SPEQ_MODE_GLOBAL", "SPEQ_MODE_LOCAL"]
 
 
@@ -370,6 +371,22 @@ class DeviceIndex:
                                             _u64p(mult), C.byref(missed), None))
         return counts, w, mult, missed.value
 
+    def dedup_fastq(self, path1: str, path2: Optional[str] = None, k: int = 21, phred_cutoff: int = 30,
+                    local: bool = False, threads: int = 4, em: Optional["EmHistogram"] = None):
+        """The scan of FASTQ(.gz) file(s) with every distinct read (pair, when path2 is given) counted once
+        (speq_dedup_fastq): two passes, fingerprints and then the masked scan. Returns (DedupStats, ScanResult), the
+        same for any `threads`; with `em` the scan also fills that histogram."""
+        G = self.n_groups
+        counts = np.zeros(G + 2, dtype=np.uint64)
+        w = np.zeros(G, dtype=np.float64) if local else None
+        p = ScanParams(k, phred_cutoff, int(path2 is not None), SPEQ_MODE_LOCAL if local else SPEQ_MODE_GLOBAL)
+        r = DedupStatsRecord()
+        check(lib().speq_dedup_fastq(self._h, em._h if em is not None else None, path1.encode(),
+                                     path2.encode() if path2 else None, C.byref(p), threads, C.byref(r),
+                                     _u64p(counts), w.ctypes.data_as(C.POINTER(C.c_double)) if w is not None else None,
+                                     None))
+        return DedupStats.from_record(r), ScanResult(int(counts[0]), int(counts[1]), counts[2:].copy(), w)
+
     AX_STATS_KEYS = ("wave_iters", "lookup_lanes", "run_lanes", "lookup_waves", "run_waves", "run_windows",
                      "deferred", "filter_pass", "p2_probes", "p2_verify", "chunks", "segments", "qual_bytes",
                      "run_tallied", "run_granules", "refills", "busy_1_4", "busy_5_16", "busy_17_32", "busy_33_64",
@@ -634,6 +651,98 @@ def bootstrap_summary_percent(percent: np.ndarray, used, estimate=None, level: f
     check(lib().speq_bootstrap_summary_percent(p.ctypes.data_as(dp), e.ctypes.data_as(dp) if e is not None else None,
                                                u.ctypes.data_as(C.POINTER(C.c_uint8)), B, G, level, out))
     return [{f: getattr(out[g], f) for f in ("estimate", "mean", "se", "lo", "hi", "used")} for g in range(G)]
+
+
+@dataclass
+class DedupStats:
+    units: int                 # N
+    distinct: int              # classes of equal fingerprint
+    max_multiplicity: int      # units of the largest class
+    mult_hist: np.ndarray      # [8] u64: classes of exactly j + 1 units (j < 7), of 8 or more (j = 7)
+
+    @classmethod
+    def from_record(cls, r: DedupStatsRecord) -> "DedupStats":
+        return cls(int(r.units), int(r.distinct), int(r.max_multiplicity),
+                   np.array(list(r.mult_hist), dtype=np.uint64))
+
+    @property
+    def duplicates(self) -> int:
+        return self.units - self.distinct
+
+
+def dedup_fingerprint(seq1: bytes, seq2: Optional[bytes] = None) -> tuple[int, int]:
+    """(F_0, F_1) of the unit (seq1, seq2) as the fingerprint kernel computes it (speq_dedup_fingerprint; host only)."""
+    out = (C.c_uint64 * 2)()
+    s2 = bytes(seq2) if seq2 is not None else None
+    lib().speq_dedup_fingerprint(bytes(seq1), len(seq1), s2, len(s2) if s2 is not None else 0, out)
+    return int(out[0]), int(out[1])
+
+
+class Dedup:
+    """Duplicate units of the reads (speq_dedup_*): add / add_device fingerprint units on the GPU, each call with the
+    index of its first unit in the input; finalize sorts them and marks, per class of equal fingerprint, the lowest
+    unit as the one that is kept; mask_device and scan then leave the others out of a scan."""
+
+    def __init__(self, dev: DeviceIndex, paired: bool = False):
+        self.dev = dev
+        self.n_groups = dev.n_groups
+        self.paired = paired
+        h = C.c_void_p()
+        check(lib().speq_dedup_create(dev.handle, int(paired), C.byref(h)))
+        self._h = h
+
+    def add(self, seq: bytes, offsets: np.ndarray, first_unit: int = 0) -> None:
+        """Host reads (staged to HBM in batches; synchronous); first_unit counts units (pairs of a paired handle)."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        check(lib().speq_dedup_add_reads(self._h, seq, _u64p(off), len(off) - 1, first_unit))
+
+    def add_device(self, d_seq: int, d_offsets: int, n_reads: int, first_unit: int = 0, stream: int = 0) -> None:
+        """HBM-resident reads (raw device pointers, like DeviceIndex.scan_device); asynchronous on `stream`."""
+        check(lib().speq_dedup_add_reads_device(self._h, d_seq or None, d_offsets or None, n_reads, first_unit,
+                                                stream or None))
+
+    def finalize(self) -> DedupStats:
+        """Waits, checks that the units added so far are 0 .. N - 1 each once, and marks the representatives."""
+        r = DedupStatsRecord()
+        check(lib().speq_dedup_finalize(self._h, C.byref(r)))
+        return DedupStats.from_record(r)
+
+    def representatives(self, first_unit: int, n_units: int) -> np.ndarray:
+        """rep[first_unit : first_unit + n_units] (u32): the lowest unit of each unit's class."""
+        rep = np.zeros(n_units, dtype=np.uint32)
+        check(lib().speq_dedup_representatives(self._h, first_unit, n_units,
+                                               rep.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return rep
+
+    def mask_device(self, d_qual: int, d_offsets: int, n_reads: int, first_unit: int = 0, stream: int = 0) -> None:
+        """Writes '!' over the qualities of the records of units that are not kept; asynchronous on `stream`."""
+        check(lib().speq_dedup_mask_device(self._h, d_qual or None, d_offsets or None, n_reads, first_unit,
+                                           stream or None))
+
+    def scan(self, seq: bytes, qual: bytes, offsets: np.ndarray, k: int, phred_cutoff: int = 30, local: bool = False,
+             first_unit: int = 0, em: Optional["EmHistogram"] = None) -> ScanResult:
+        """DeviceIndex.scan of the reads with every unit that is not kept left out (speq_dedup_scan_reads); with `em`
+        the scan also fills that histogram."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        G = self.n_groups
+        counts = np.zeros(G + 2, dtype=np.uint64)
+        w = np.zeros(G, dtype=np.float64) if local else None
+        p = ScanParams(k, phred_cutoff, int(self.paired), SPEQ_MODE_LOCAL if local else SPEQ_MODE_GLOBAL)
+        check(lib().speq_dedup_scan_reads(self._h, em._h if em is not None else None, seq, qual, _u64p(off),
+                                          len(off) - 1, first_unit, C.byref(p), _u64p(counts),
+                                          w.ctypes.data_as(C.POINTER(C.c_double)) if w is not None else None))
+        return ScanResult(int(counts[0]), int(counts[1]), counts[2:].copy(), w)
+
+    def close(self):
+        if self._h:
+            lib().speq_dedup_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Comm:

@@ -43,6 +43,7 @@ struct CmdArguments {  // include/arg_parse.h:10-28
     unsigned int bootstrap_replicates{200};       // --bootstrap-replicates
     uint64_t bootstrap_seed{1};                   // --bootstrap-seed
     double bootstrap_level{0.95};                 // --bootstrap-level
+    std::filesystem::path out_file_dedup{};       // --dedup: the percentages with every distinct read (pair) counted once
 };
 
 struct ParseError : std::runtime_error {

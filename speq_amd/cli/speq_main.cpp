@@ -73,6 +73,12 @@ const char* HELP =
     "      --bootstrap-replicates N  resamplings, 1..1024 (default 200)\n"
     "      --bootstrap-seed S    seed of the resampling weights (default 1)\n"
     "      --bootstrap-level L   two-sided level of lo..hi, in (0,1) (default 0.95)\n"
+    "      --dedup FILE          scan: after the scan, two more passes over the reads count every distinct read (pair)\n"
+    "                            once: reads (pairs) of the same bases, whatever their qualities, are duplicates and the\n"
+    "                            first one in the file is kept. FILE: '#' lines with units, distinct, duplicates,\n"
+    "                            duplicate_fraction, max_multiplicity and multiplicity_hist, then name, percent,\n"
+    "                            percent_dedup, refined, refined_dedup (tab-separated): the run's initial and EM-refined\n"
+    "                            percentages beside the same from the deduplicated reads\n"
     "one process per GPU: run under a launcher that sets WORLD_SIZE > 1, RANK and LOCAL_RANK (e.g. torchrun\n"
     "--no-python bin/speq scan ...): each rank scans its share of the reads on GPU $LOCAL_RANK and the counts are\n"
     "summed with RCCL; rank 0 prints and writes the results ($SPEQ_RENDEZVOUS: the id file, default under /tmp)\n";
@@ -174,6 +180,7 @@ CmdArguments parse(int argc, char** argv) {
         else if (allow_reads && opt == "--bootstrap-replicates") a.bootstrap_replicates = to_number<unsigned>(opt, value());
         else if (allow_reads && opt == "--bootstrap-seed") a.bootstrap_seed = to_number<uint64_t>(opt, value());
         else if (allow_reads && opt == "--bootstrap-level") a.bootstrap_level = to_number<double>(opt, value());
+        else if (allow_reads && opt == "--dedup") a.out_file_dedup = value();
         else if (allow_reads && opt == "--max-em-iterations") a.max_em_iterations = to_number<unsigned>(opt, value());
         else throw ParseError("Unknown option " + opt + ". In case this is meant to be a non-option/argument/parameter, "
                               "please specify the start of non-options with '--'.");
@@ -217,6 +224,7 @@ CmdArguments parse(int argc, char** argv) {
     if (!a.out_file_marker_coverage.empty()) check_out_file(a.out_file_marker_coverage, a.is_force);
     if (!a.out_file_bootstrap.empty()) check_out_file(a.out_file_bootstrap, a.is_force);
     if (!a.out_file_bootstrap_em.empty()) check_out_file(a.out_file_bootstrap_em, a.is_force);
+    if (!a.out_file_dedup.empty()) check_out_file(a.out_file_dedup, a.is_force);
     a.is_parsed = true;
     return a;
 }
@@ -658,6 +666,89 @@ void write_bootstrap(const CmdArguments& a, speq_device_index* d, const speq_sca
     write_table(a.out_file_bootstrap_em, names, ci);
 }
 
+// The refinement loop of `speq scan` (fm_scanner.cpp:248-279, :515-545, :761-792, :1035-1065) over a finalized
+// histogram: steps until the largest change of a percentage is within --precision-cutoff, or --max-em-iterations steps
+// were made. `print`: the run's own refinement writes what the reference writes to stderr per step; --dedup's runs the
+// same loop on the deduplicated counters and prints nothing.
+std::vector<double> refine_percentages(const CmdArguments& a, const speq_em* em, std::vector<double> percent,
+                                       const std::vector<double>& unique_totals, uint64_t total,
+                                       const std::vector<uint64_t>& unique, const std::vector<int32_t>& group_counts,
+                                       bool local, bool paired, bool print) {
+    const size_t G = percent.size();
+    std::vector<double> diff(G, 1.0), next(G);
+    for (unsigned it = 0; G > 0 && *std::max_element(diff.begin(), diff.end()) > a.precision; ++it) {
+        if (it >= a.max_em_iterations) {
+            if (print) std::cerr << "speq: EM stopped after " << it << " iterations (--max-em-iterations)\n";
+            break;
+        }
+        ok(speq_em_step(em, percent.data(), group_counts.data(), unique.data(), next.data()), "EM step");
+        if (print && local && !paired)
+            std::cerr << "1: " << speq::format_vector(unique_totals) << "\n2: " << total << "\n3: "
+                      << speq::format_vector(next) << "\n";
+        std::vector<double> np = unique_to_percent(unique_totals, total, unique_totals, next);
+        for (size_t i = 0; i < G; ++i) diff[i] = std::fabs(np[i] - percent[i]);
+        percent = np;
+        if (!print) continue;
+        if (local && !paired) {
+            std::cerr << "Percent of each group: " << speq::format_vector(percent) << "\n";
+            std::cerr << "Total Kmers per group: " << speq::format_vector(next) << "\n\n";
+        } else {
+            std::cerr << speq::format_vector(percent) << "\n" << speq::format_vector(next) << "\n\n";
+        }
+    }
+    return percent;
+}
+
+// FILE of --dedup: '#' lines with the duplicate statistics, a header line, then per group (groupings order) its name,
+// the run's initial and refined percentages, and the same two from the reads with every distinct read (pair) counted
+// once. The deduplicated scan fills a histogram of its own, which the run's own refinement loop then refines.
+void write_dedup(const CmdArguments& a, const speq_index* idx, speq_device_index* d, const speq_scan_params& prm,
+                 const std::vector<std::string>& names, const std::vector<uint64_t>& u_ref,
+                 const std::vector<uint64_t>& tot_ref, const std::vector<int32_t>& group_counts,
+                 const std::vector<double>& initial, const std::vector<double>& refined) {
+    const size_t G = names.size();
+    const bool local = prm.mode == SPEQ_MODE_LOCAL, paired = prm.paired != 0;
+    speq_em* em = nullptr;
+    ok(speq_em_create(idx, d, &em), "allocating the EM histogram");
+    struct Free {
+        speq_em* e;
+        ~Free() { speq_em_free(e); }
+    } free_em{em};
+    std::vector<uint64_t> counts(G + 2, 0);
+    std::vector<double> weights(std::max<size_t>(G, 1), 0.0);
+    speq_dedup_stats ds{};
+    ok(speq_dedup_fastq(d, em, a.in_file_reads_path_1.c_str(),
+                        a.in_file_reads_path_2.empty() ? nullptr : a.in_file_reads_path_2.c_str(), &prm, a.threads, &ds,
+                        counts.data(), local ? weights.data() : nullptr, nullptr),
+       "deduplicating the reads");
+    ok(speq_em_finalize(em, a.threads), "building the EM histogram");
+    const uint64_t total = counts[0];
+    std::vector<double> unique_totals(G, 0.0);
+    if (local) {
+        unique_totals.assign(weights.begin(), weights.begin() + G);
+    } else {
+        const double percent_perfect = std::pow(a.fixed_accuracy, (double)a.kmer);
+        for (size_t i = 0; i < G; ++i) unique_totals[i] = static_cast<double>(counts[2 + i]) / percent_perfect;
+    }
+    const std::vector<double> first = unique_to_percent(unique_totals, total, to_double(u_ref), to_double(tot_ref));
+    const std::vector<uint64_t> unique(counts.begin() + 2, counts.end());
+    const std::vector<double> last =
+        refine_percentages(a, em, first, unique_totals, total, unique, group_counts, local, paired, false);
+    std::ofstream of(a.out_file_dedup);
+    if (!of) throw CApiError("cannot write " + a.out_file_dedup.string());
+    char buf[400];
+    std::snprintf(buf, sizeof buf, "%.6f", ds.units ? (double)(ds.units - ds.distinct) / (double)ds.units : 0.0);
+    of << "# units " << ds.units << "\n# distinct " << ds.distinct << "\n# duplicates " << ds.units - ds.distinct
+       << "\n# duplicate_fraction " << buf << "\n# max_multiplicity " << ds.max_multiplicity
+       << "\n# multiplicity_hist";
+    for (int j = 0; j < SPEQ_DEDUP_BINS; ++j) of << " " << ds.mult_hist[j];
+    of << "\nname\tpercent\tpercent_dedup\trefined\trefined_dedup\n";
+    for (size_t g = 0; g < G; ++g) {
+        std::snprintf(buf, sizeof buf, "\t%.6f\t%.6f\t%.6f\t%.6f\n", initial[g], first[g], refined[g], last[g]);
+        of << names[g] << buf;
+    }
+}
+
 int run_scan(CmdArguments& a) {
     PhaseClock phase;
     Dist dd = dist_from_env(a);
@@ -874,27 +965,9 @@ int run_scan(CmdArguments& a) {
             std::fprintf(stderr, "speq: EM histogram: %llu intervals, %llu (group, count) entries, %llu windows\n",
                          (unsigned long long)rows, (unsigned long long)ents, (unsigned long long)wins);
     }
+    const std::vector<double> initial = percent;  // the first vector printed above (--dedup's `percent` column)
     std::vector<uint64_t> unique(counts.begin() + 2, counts.end());
-    std::vector<double> diff(G, 1.0), next(G);
-    for (unsigned it = 0; G > 0 && *std::max_element(diff.begin(), diff.end()) > a.precision; ++it) {
-        if (it >= a.max_em_iterations) {
-            std::cerr << "speq: EM stopped after " << it << " iterations (--max-em-iterations)\n";
-            break;
-        }
-        ok(speq_em_step(em, percent.data(), h.counts.data(), unique.data(), next.data()), "EM step");
-        if (local && !paired)
-            std::cerr << "1: " << speq::format_vector(unique_totals) << "\n2: " << total << "\n3: "
-                      << speq::format_vector(next) << "\n";
-        std::vector<double> np = unique_to_percent(unique_totals, total, unique_totals, next);
-        for (size_t i = 0; i < G; ++i) diff[i] = std::fabs(np[i] - percent[i]);
-        percent = np;
-        if (local && !paired) {
-            std::cerr << "Percent of each group: " << speq::format_vector(percent) << "\n";
-            std::cerr << "Total Kmers per group: " << speq::format_vector(next) << "\n\n";
-        } else {
-            std::cerr << speq::format_vector(percent) << "\n" << speq::format_vector(next) << "\n\n";
-        }
-    }
+    percent = refine_percentages(a, em, percent, unique_totals, total, unique, h.counts, local, paired, true);
     phase("EM iterations");
 
     // The reference writes nothing to -o (quirk B1); we write the (refined) percentage vector there.
@@ -923,6 +996,12 @@ int run_scan(CmdArguments& a) {
     if (!a.out_file_bootstrap.empty() || !a.out_file_bootstrap_em.empty()) {
         write_bootstrap(a, d, prm, h.names, u_ref, tot_ref, em, h.counts, percent);
         phase("bootstrap");
+    }
+    // --dedup: two more passes over the same reads, placed like --group-sets: the percentages with every distinct read
+    // (pair) counted once, beside the run's own.
+    if (!a.out_file_dedup.empty()) {
+        write_dedup(a, idx, d, prm, h.names, u_ref, tot_ref, h.counts, initial, percent);
+        phase("dedup");
     }
     speq_em_free(em);
     // The device replica, its pinned pipeline slots and the index are left to process exit: unpinning and freeing

@@ -927,6 +927,53 @@ struct BootstrapSink final : HostSink {
     }
 };
 
+// Pass 1 of speq_dedup_fastq: the fingerprints of every host-parsed block (speq_dedup_add_reads) into one handle; a
+// unit's index is its position in the file, which the block's first record gives.
+struct DedupSink final : HostSink {
+    speq_dedup* h;
+    uint32_t per;  // records per unit
+    DedupSink(speq_dedup* handle, bool paired) : h(handle), per(paired ? 2u : 1u) {}
+    void submit(const speq_slot& s, uint64_t records) override {
+        Release rel{*this, s.slot};
+        if (records != 0) throw std::logic_error("the dedup sink needs the block's first record");
+    }
+    void submit_at(const speq_slot& s, uint64_t records, uint64_t first_record) override {
+        Release rel{*this, s.slot};
+        if (records == 0) return;
+        check_rc(speq_dedup_add_reads(h, s.seq, s.offsets, records, first_record / per));
+    }
+};
+
+// Pass 2: the masked scan of every block (speq_dedup_scan_reads) after the handle's finalize. A block's counters come
+// back on their own and are added to the totals under the sink's lock: integer adds, so the blocks' order does not
+// matter to the counts (the local weights are f64 sums of the blocks' sums in arrival order).
+struct DedupScanSink final : HostSink {
+    speq_dedup* h;
+    speq_em* em;
+    speq_scan_params params;
+    uint32_t per;
+    std::vector<uint64_t> counts;
+    std::vector<double> weights;
+    DedupScanSink(speq_dedup* handle, speq_em* hist, const speq_scan_params& p, uint32_t G)
+        : h(handle), em(hist), params(p), per(p.paired ? 2u : 1u), counts(SPEQ_COUNTS_LEN(G), 0),
+          weights(std::max<uint32_t>(G, 1), 0.0) {}
+    void submit(const speq_slot& s, uint64_t records) override {
+        Release rel{*this, s.slot};
+        if (records != 0) throw std::logic_error("the dedup sink needs the block's first record");
+    }
+    void submit_at(const speq_slot& s, uint64_t records, uint64_t first_record) override {
+        Release rel{*this, s.slot};
+        if (records == 0) return;
+        std::vector<uint64_t> c(counts.size(), 0);
+        std::vector<double> w(weights.size(), 0.0);
+        check_rc(speq_dedup_scan_reads(h, em, s.seq, s.qual, s.offsets, records, first_record / per, &params, c.data(),
+                                       w.data()));
+        std::lock_guard<std::mutex> lk(mu);
+        for (size_t i = 0; i < c.size(); ++i) counts[i] += c[i];
+        for (size_t i = 0; i < w.size(); ++i) weights[i] += w[i];
+    }
+};
+
 // Pinned slot size of speq_scan_fastq's pipeline: a block pair of up to 12 MiB per file plus one record usually
 // fits (larger blocks grow their slot once: speq_pipeline_reserve).
 constexpr uint64_t SLOT_BYTES = 16ull << 20;
@@ -1650,6 +1697,42 @@ extern "C" int speq_bootstrap_em_fastq(speq_device_index* d, const speq_em* em, 
     }
     return bootstrap_fastq_impl("speq_bootstrap_em_fastq", d, em, path1, path2, params, replicates, seed, threads,
                                 counts, weights, mult, missed, stats);
+}
+
+extern "C" int speq_dedup_fastq(speq_device_index* d, speq_em* em, const char* path1, const char* path2,
+                                const speq_scan_params* params, uint32_t threads, speq_dedup_stats* stats,
+                                uint64_t* counts, double* weights, speq_stream_stats* st) {
+    const char* who = "speq_dedup_fastq";
+    const auto t0 = std::chrono::steady_clock::now();
+    speq_scan_params p{};
+    int rc = speq::guarded([&] {
+        if (!params) throw std::invalid_argument(std::string(who) + ": null params");
+        if (!d || !path1 || !counts || (params->mode == SPEQ_MODE_LOCAL && !weights))
+            throw std::invalid_argument(std::string(who) + ": null argument");
+        p = *params;
+        p.paired = path2 != nullptr;
+    });
+    if (rc != SPEQ_OK) return rc;
+    speq_dedup* h = nullptr;
+    rc = speq_dedup_create(d, p.paired, &h);
+    if (rc != SPEQ_OK) return rc;
+    rc = speq::guarded([&] {
+        {
+            DedupSink sink(h, p.paired != 0);
+            (void)run_stream(path1, path2, threads, sink, false, false);
+        }
+        speq_dedup_stats ds{};
+        check_rc(speq_dedup_finalize(h, &ds));
+        if (stats) *stats = ds;
+        const uint32_t G = speq::device_groups(d);
+        DedupScanSink sink(h, em, p, G);
+        const StreamTotals tot = run_stream(path1, path2, threads, sink, false, false);
+        std::copy(sink.counts.begin(), sink.counts.end(), counts);
+        if (p.mode == SPEQ_MODE_LOCAL) std::copy(sink.weights.begin(), sink.weights.begin() + G, weights);
+        fill_stats(st, tot, t0);
+    });
+    speq_dedup_free(h);
+    return rc;
 }
 
 extern "C" uint64_t speq_group_sets_count(const speq_group_sets* s) { return s ? s->units.size() : 0; }
