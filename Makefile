@@ -86,6 +86,8 @@ AXKNOB_kv1 := -DSPEQ_AX_SU=1 -DSPEQ_AX_SU_LOCAL=2 -DSPEQ_AX_REFILL=8 -DSPEQ_AX_B
 AXKNOB_kv2 := -DSPEQ_AX_WPB=2 -DSPEQ_AX_MIN_WAVES=4 -DSPEQ_AX_MIN_WAVES_LOCAL=3 -DSPEQ_AX_DEF_GLOBAL=192 -DSPEQ_AX_DEF_LOCAL=128
 AXKNOB_kv3 := -DSPEQ_AX_SPEC_HW=1 -DSPEQ_AX_PRIO=0 -DSPEQ_AX_MPROOF=0
 AXKNOB_kv4 := -DSPEQ_AX_SPROOF=0
+# (kv3 also stages every batch with all its stream instructions)
+AXKNOB_kv3 += -DSPEQ_AX_STAGE_SKIP=0
 AXKNOBS    := kv1 kv2 kv3 kv4
 AXKNOB_OTHER := $(filter-out $(OBJDIR)/ax_scan.o,$(LIB_OBJS))
 

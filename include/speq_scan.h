@@ -160,10 +160,11 @@ int speq_scan_reads_device(speq_device_index* d, const uint8_t* d_seq, const uin
  * batches, [30] the longest wave's loop cycles (a maximum), [31] waves, [32..36] loop cycles summed over the waves of
  * blocks 0-255, 256-511, 512-767, 768-1023 and 1024 on, [37] probes of the substitution bitmap (tuning "ax_sproof"),
  * [38] windows over a mismatch dropped on its proof (not looked up, not deferred), [39] proofs whose continued run met
- * a second mismatch within k - 1 bases (the windows over both deferred). Fails with SPEQ_E_ARG when the scan does not
+ * a second mismatch within k - 1 bases (the windows over both deferred), [40] 64-chunk stream instructions the
+ * staging batches executed (per wave; [10] / 64 are needed). Fails with SPEQ_E_ARG when the scan does not
  * use that kernel, and, before anything is launched (counts, weights and stats untouched), when the replica has more
  * than 2048 groups: the instrumented kernel exists with the LDS tally only. */
-#define SPEQ_AX_STATS_N 40
+#define SPEQ_AX_STATS_N 41
 int speq_scan_reads_device_stats(speq_device_index* d, const uint8_t* d_seq, const uint8_t* d_qual,
                                  const uint64_t* d_offsets, uint64_t n_reads, const speq_scan_params* params,
                                  uint64_t* d_counts, double* d_weights, uint64_t* stats);

@@ -393,7 +393,7 @@ class DeviceIndex:
                      "cyc_refill", "cyc_lookup", "cyc_run", "cyc_phase2", "cyc_total", "p2_passes",
                      "cyc_p2_filter", "p2_rounds", "cyc_ref_pre", "cyc_ref_stage", "cyc_wave_max", "waves",
                      "cyc_gen0", "cyc_gen1", "cyc_gen2", "cyc_gen3", "cyc_gen4",
-                     "sproof_probes", "sproof_windows", "sproof_partial")
+                     "sproof_probes", "sproof_windows", "sproof_partial", "stage_slots")
 
     def scan_device_stats(self, d_seq: int, d_qual: int, d_offsets: int, n_reads: int, k: int, d_counts: int,
                           d_weights: int = 0, phred_cutoff: int = 30, paired: bool = False,

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "ax_decode.hpp"
 #include "scan_device.hpp"
 #include "speq_scan.h"
 
@@ -37,7 +38,7 @@ namespace {
 using namespace speq_dev;
 
 // Compile-time knobs (A/B only; every one is run through the parity tests forced to a non-default value by
-// tests/test_gpu_ax_knobs.py and tests/test_gpu_sproof_knob.py over `make axknobs` builds), seventeen: SPEQ_AX_DEF_LOCAL, SPEQ_AX_DEF_GLOBAL, SPEQ_AX_WL,
+// tests/test_gpu_ax_knobs.py and tests/test_gpu_sproof_knob.py over `make axknobs` builds), eighteen: SPEQ_AX_STAGE_SKIP, SPEQ_AX_DEF_LOCAL, SPEQ_AX_DEF_GLOBAL, SPEQ_AX_WL,
 // SPEQ_AX_WPB, SPEQ_AX_SU, SPEQ_AX_SU_LOCAL, SPEQ_AX_MIN_WAVES, SPEQ_AX_MIN_WAVES_LOCAL, SPEQ_AX_REFILL, SPEQ_AX_BLOCKED,
 // SPEQ_AX_SPEC_HW, SPEQ_AX_PRIO, SPEQ_AX_PRIO_MIN, SPEQ_AX_P2_MARGIN, SPEQ_AX_MPROOF, SPEQ_AX_MTILES, SPEQ_AX_SPROOF.
 // Measured losers
@@ -127,6 +128,7 @@ enum : uint32_t {
     AXS_SPROOF_PROBES,   // probes of the substitution bitmap (lanes in state 7)
     AXS_SPROOF_WINDOWS,  // valid windows over a mismatch dropped on its proof (neither looked up nor deferred)
     AXS_SPROOF_PARTIAL,  // proofs whose continued run met a second mismatch within k - 1 bases
+    AXS_STAGE_SLOTS,     // 64-chunk stream instructions the staging batches executed (per wave; needed: chunks / 64)
     AXS_N
 };
 static_assert(AXS_N == SPEQ_AX_STATS_N, "speq_scan.h SPEQ_AX_STATS_N");
@@ -274,8 +276,14 @@ static_assert(AX_WL % 64u == 0 && AX_WL >= 64u && AX_WL <= 512u, "work list: 1-8
 #ifndef SPEQ_AX_SU  // staging: stream instructions per load batch, global mode (A/B knob). 3 since round 6: the
 #define SPEQ_AX_SU 3   // staging code hoisted out of the refill branch left the registers for it at 5 waves/SIMD
 #endif                 // (round 4's 3 spilled 20-36 B per lane); k 65-96 and paired k 33-64 keep 2 (3 spills there)
-#ifndef SPEQ_AX_SU_LOCAL  // the same, Phred-weighted mode (4 waves/SIMD, 128 VGPRs; A/B knob)
-#define SPEQ_AX_SU_LOCAL 3
+#ifndef SPEQ_AX_SU_LOCAL  // the same, Phred-weighted mode (A/B knob): 3 at every k and paired too — at 4 waves/SIMD
+#define SPEQ_AX_SU_LOCAL 3   // its 128 VGPRs hold three instructions without scratch (profiles/r09/ax_regs_new.txt),
+#endif                       // so the drop to 2 for k 65-96 and paired k 33-64 is global mode's alone
+// SPEQ_AX_STAGE_SKIP 1: a batch executes only the stream instructions that hold a chunk of the group (its last batch:
+// 1 .. SU of them); 0: all SU, the lanes past the end clamped (A/B switch; forced to 0 in the `kv3`
+// build of `make axknobs`, so the knob suite runs that path too)
+#if !defined(SPEQ_AX_STAGE_SKIP)
+#define SPEQ_AX_STAGE_SKIP 1
 #endif
 template <int MODE, bool PAIRED, int HW>
 constexpr uint32_t ax_su() {

@@ -440,14 +440,13 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
     const uint64_t gw = (uint64_t)blockIdx.x * AX_WPB + wid;
     const uint64_t nu = PAIRED ? src.n_units / 2 : src.n_units;  // units: reads, or mate pairs
     const uint32_t segw = AX_CAP - k + 1u;  // windows per segment
-    const uint32_t qt = 33u + src.cutoff;   // Phred+33 byte <= qt  <=>  clamp(q, 0, 41) <= cutoff (cutoff < 41)
-    const uint32_t qt4 = (qt > 0x7Fu ? 0x7Fu : qt) * 0x01010101u;
-    const uint32_t allbad = src.cutoff >= 41u ? 0x80808080u : 0u;  // every window fails the quality filter
+    // Phred+33 byte <= 33 + cutoff  <=>  clamp(q, 0, 41) <= cutoff (cutoff < 41); from 41 on every window fails
+    const uint32_t qt4 = axd_qt4(src.cutoff), allbad = axd_allbad(src.cutoff);
 
     // diagnostic counters (STATS only; wave-level ones are counted by lane 0)
     uint32_t s_iter = 0, s_lk = 0, s_rn = 0, s_lkw = 0, s_rnw = 0, s_rwin = 0, s_def = 0, s_fp = 0, s_p2 = 0,
              s_p2v = 0, s_ch = 0, s_seg = 0, s_qb = 0, s_tal = 0, s_rg = 0, s_spl = 0, s_b4 = 0, s_b16 = 0, s_b32 = 0,
-             s_b64 = 0, s_p2n = 0, s_p2r = 0, s_spp = 0, s_spw = 0, s_spt = 0;
+             s_b64 = 0, s_p2n = 0, s_p2r = 0, s_spp = 0, s_spw = 0, s_spt = 0, s_slots = 0;
     // section clocks (STATS only; wave-uniform, kept by every lane, reported by lane 0)
     uint64_t c_ref = 0, c_lk = 0, c_rn = 0, c_p2 = 0, c_p2f = 0, c_rpre = 0, c_rstg = 0, c_t0 = STATS ? clock64() : 0ull, c_s = 0;
 
@@ -720,23 +719,35 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
     constexpr uint32_t SU = ax_su<MODE, PAIRED, HW>();  // stream instructions of one batch
     static_assert(64u * SU <= ax_ownb<MODE>(), "owner map of one batch");
     static_assert(AX_CHUNKS < 16, "chunk counts in four bits");
+    static_assert(SU >= 1u && SU <= 4u, "stage_batch is instantiated for 1 .. 4 stream instructions");
     uint32_t stg_tot = 0;      // (wave-uniform) the group's chunks
     uint32_t stg_ocarry = 0;   // (wave-uniform) owner mark of the last chunk of the previous 64
     uint32_t stg_qcarry = 0;   // (wave-uniform, local) last quality dword of the previous instruction's lane 63
     uint32_t stg_pre = 0, stg_nch = 0;  // this lane's piece: first chunk in the group's stream, chunks (0: none)
-    // owners and loads of the batch from chunk c0: every refilling lane marks the first chunk of its range in a byte
-    // map (lane + 1); a prefix max over the lanes (DPP; owners grow with the chunk index) spreads the mark over the
-    // range, and the last owner carries into the next 64 chunks. dst[u] = the owner's slot word (ci * 64 + owner).
-    auto stage_issue = [&](uint32_t c0, uint4(&sv)[SU], uint4(&qv)[SU], uint32_t(&dst)[SU]) {
+    // One batch of N stream instructions from chunk c0 (N <= SU, a compile-time count: the arrays of the loads in
+    // flight stay in registers and each N is straight-line code; a run-time count over one unrolled body spilled 32-112
+    // B per lane in every instantiation). A group's batches run all SU but its last, which runs the
+    // 1 .. SU instructions that hold a chunk of the group (SPEQ_AX_STAGE_SKIP 0: all SU, the lanes past the end
+    // clamped to the last chunk and their stores masked).
+    // Owners and loads: every refilling lane marks the first chunk of its range in a byte map (lane + 1; a range
+    // starts before stg_tot, so every mark of the batch falls into an executed instruction); a prefix max over the
+    // lanes (DPP; owners grow with the chunk index) spreads the mark over the range, and the last owner carries into
+    // the next 64 chunks. dst[u] = the owner's slot word (ci * 64 + owner). All N instructions' loads are issued
+    // before the decode waits for the first: 2-bit codes, bad-base bits, quality changes (ax_decode.hpp) into the
+    // owners' slots.
+    auto stage_batch = [&](auto n_const, uint32_t c0) __attribute__((always_inline)) {
+        constexpr uint32_t N = decltype(n_const)::value;
+        uint4 sv[N], qv[N];
+        uint32_t dst[N];
 #pragma unroll
-        for (uint32_t u = 0; u < SU; ++u) ownb[64u * u + lane] = 0;
-        if (stg_nch != 0u && stg_pre >= c0 && stg_pre < c0 + 64u * SU) ownb[stg_pre - c0] = (uint8_t)(lane + 1u);
+        for (uint32_t u = 0; u < N; ++u) ownb[64u * u + lane] = 0;
+        if (stg_nch != 0u && stg_pre >= c0 && stg_pre < c0 + 64u * N) ownb[stg_pre - c0] = (uint8_t)(lane + 1u);
         wave_sync();
-        uint32_t mk[SU];
+        uint32_t mk[N];
 #pragma unroll
-        for (uint32_t u = 0; u < SU; ++u) mk[u] = ownb[64u * u + lane];
+        for (uint32_t u = 0; u < N; ++u) mk[u] = ownb[64u * u + lane];
 #pragma unroll
-        for (uint32_t u = 0; u < SU; ++u) {
+        for (uint32_t u = 0; u < N; ++u) {
             const uint32_t c = min(c0 + 64u * u + lane, stg_tot - 1u);
             uint32_t m = mk[u];
             m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x111, 0xF, 0xF, false));  // row_shr:1
@@ -755,11 +766,11 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
             sv[u] = *reinterpret_cast<const uint4*>(src.seq + go);
             qv[u] = *reinterpret_cast<const uint4*>(src.qual + go);
         }
-    };
-    // decodes the batch from chunk c0 into the owners' slots: 2-bit codes, bad-base bits, quality changes
-    auto stage_decode = [&](uint32_t c0, const uint4(&sv)[SU], const uint4(&qv)[SU], const uint32_t(&dst)[SU]) {
+        // (the scheduler may not sink a load below this point: without it the batch of one instruction decoded the
+        // bases before it issued the load of the qualities, two round trips in a row)
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (uint32_t u = 0; u < SU; ++u) {
+        for (uint32_t u = 0; u < N; ++u) {
             const uint32_t c = c0 + 64u * u + lane;
             const uint32_t sd[4] = {sv[u].x, sv[u].y, sv[u].z, sv[u].w};
             const uint32_t qd[4] = {qv[u].x, qv[u].y, qv[u].z, qv[u].w};
@@ -769,25 +780,10 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
             uint32_t qprev = 0;
             if (MODE == KM_LOCAL) {  // the previous chunk's last quality (the previous lane's, or the carry)
                 const uint32_t up = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)qv[u].w, 0x138, 0xF, 0xF, false);
-                qprev = lane == 0 ? stg_qcarry : up;
+                qprev = (lane == 0 ? stg_qcarry : up) >> 24;
                 stg_qcarry = __builtin_amdgcn_readlane(qv[u].w, 63);
             }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const uint32_t x = sd[i] | 0x20202020u;  // lower case
-                const uint32_t c4 = ((x >> 1) ^ (x >> 2)) & 0x03030303u;  // a c g t/u -> 0 1 2 3
-                cw |= ((c4 | (c4 >> 6) | (c4 >> 12) | (c4 >> 18)) & 0xFFu) << (8 * i);
-                const uint32_t canon = __builtin_amdgcn_perm(0u, 0x74676361u, c4);  // the letter of that code
-                const uint32_t okb = zero_bytes(x ^ canon) | zero_bytes(x ^ 0x75757575u);  // ACGT or U
-                const uint32_t y = qd[i];
-                const uint32_t badq = (((0x80808080u | qt4) - (y & 0x7F7F7F7Fu)) & ~y & 0x80808080u) | allbad;
-                bad |= flags4((~okb & 0x80808080u) | badq) << (4 * i);
-                if (MODE == KM_LOCAL) {
-                    const uint32_t prev = (y << 8) | (qprev >> 24);
-                    chb |= flags4(~zero_bytes(y ^ prev) & 0x80808080u) << (4 * i);
-                    qprev = y;
-                }
-            }
+            ax_decode_chunk<MODE == KM_LOCAL>(sd, qd, qt4, allbad, qprev, cw, bad, chb);
             if (c < stg_tot) {
                 const uint32_t ci = dst[u] >> 6, o = dst[u] & 63u;
                 codes[dst[u]] = cw;
@@ -1089,12 +1085,16 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                 c_b = clock64();
                 c_rpre += c_b - c_s;
             }
-            for (uint32_t c0 = 0; c0 < nch_tot; c0 += 64u * SU) {
-                uint4 sv[SU], qv[SU];
-                uint32_t dst[SU];
-                stage_issue(c0, sv, qv, dst);
-                stage_decode(c0, sv, qv, dst);
-            }
+            // the whole batches, then the group's last stream instructions as a batch of their own size
+            const uint32_t slots = (nch_tot + 63u) / 64u;  // stream instructions that hold a chunk
+            const uint32_t full = SPEQ_AX_STAGE_SKIP ? slots / SU : (slots + SU - 1u) / SU;
+            for (uint32_t b = 0; b < full; ++b) stage_batch(std::integral_constant<uint32_t, SU>{}, 64u * SU * b);
+            const uint32_t c1 = 64u * SU * full;
+            const uint32_t ns = SPEQ_AX_STAGE_SKIP ? slots % SU : 0u;  // 0 .. SU - 1
+            if (SU > 1u && ns == 1u) stage_batch(std::integral_constant<uint32_t, 1u>{}, c1);
+            if (SU > 2u && ns == 2u) stage_batch(std::integral_constant<uint32_t, (SU > 2u ? 2u : 1u)>{}, c1);
+            if (SU > 3u && ns == 3u) stage_batch(std::integral_constant<uint32_t, (SU > 3u ? 3u : 1u)>{}, c1);
+            if (STATS) s_slots += lane == 0 ? SU * full + ns : 0u;
             wave_sync();
             if (STATS) c_rstg += clock64() - c_b;
             if (stg) finish_piece(nch);
@@ -1705,7 +1705,7 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                                     lane == 0 ? c_p2 : 0ull, lane == 0 ? c_tot : 0ull, s_p2n,
                                     lane == 0 ? c_p2f : 0ull, s_p2r, lane == 0 ? c_rpre : 0ull,
                                     lane == 0 ? c_rstg : 0ull, 0ull, lane == 0 ? 1ull : 0ull, 0ull, 0ull, 0ull, 0ull,
-                                    0ull, s_spp, s_spw, s_spt};
+                                    0ull, s_spp, s_spw, s_spt, s_slots};
 #pragma unroll
         for (uint32_t i = 0; i < AXS_N; ++i)
             if (sv[i]) atomicAdd(&A.stats[i], (unsigned long long)sv[i]);
