@@ -20,7 +20,7 @@ LIB_HIP  := speq_amd/csrc/scan_kernels.hip speq_amd/csrc/ax_scan.hip speq_amd/cs
             speq_amd/csrc/read_dedup.hip
 LIB_CPP  := speq_amd/csrc/sais.cpp speq_amd/csrc/fm_index.cpp speq_amd/csrc/capi.cpp speq_amd/csrc/comm.cpp \
             speq_amd/csrc/host_io.cpp speq_amd/csrc/em.cpp speq_amd/csrc/pipeline.cpp \
-            speq_amd/csrc/fastq_stream.cpp
+            speq_amd/csrc/fastq_stream.cpp speq_amd/csrc/dev_mem.cpp
 CLI_CPP  := speq_amd/cli/speq_main.cpp
 
 LIB_OBJS := $(patsubst speq_amd/csrc/%.hip,$(OBJDIR)/%.o,$(LIB_HIP)) \
@@ -41,7 +41,7 @@ $(OBJDIR)/%.o: speq_amd/csrc/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # host-only translation units that call the HIP runtime / RCCL API (no kernels): g++ with the ROCm headers
-$(OBJDIR)/comm.o $(OBJDIR)/pipeline.o: $(OBJDIR)/%.o: speq_amd/csrc/%.cpp $(HDRS)
+$(OBJDIR)/comm.o $(OBJDIR)/pipeline.o $(OBJDIR)/dev_mem.o: $(OBJDIR)/%.o: speq_amd/csrc/%.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(CXX) $(HOSTFLAGS) -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -c $< -o $@
 

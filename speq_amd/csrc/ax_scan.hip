@@ -1800,131 +1800,107 @@ AxTable build_ax(speq_device_index* d, uint32_t k) {
         ax.transient = true;
         return ax;
     }
-    uint32_t* owner = nullptr;
-    uint8_t* codes = nullptr;
-    uint32_t* sa = nullptr;
-    unsigned long long* d_cnt = nullptr;
-    std::vector<void*> mine;  // this table's allocations (tracked by the replica once the table is complete)
-    auto cleanup = [&] {
-        (void)hipStreamSynchronize(d->stream);
-        for (void** q : {reinterpret_cast<void**>(&owner), reinterpret_cast<void**>(&codes),
-                         reinterpret_cast<void**>(&sa), reinterpret_cast<void**>(&d_cnt)}) {
-            if (*q) (void)hipFree(*q);
-            *q = nullptr;
-        }
-    };
-    auto alloc = [&](void** pp, uint64_t bytes) {
-        HIP_OK(hipMalloc(pp, bytes));
-        mine.push_back(*pp);
-    };
-    try {
-        if (!d->d_text2) {  // 2-bit text + non-ACGT bitmap, once per replica
-            HIP_OK(hipMalloc(&d->d_text2, nw64 * 16));
-            d->track(d->d_text2);
-            HIP_OK(hipMalloc(&d->d_tbad, nw64 * 8));
-            d->track(d->d_tbad);
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((nw64 + 255) / 256, 4096);
-            hipLaunchKernelGGL(k_ax_text2, dim3(grid), dim3(256), 0, d->stream, d->d_text, n, d->d_text2, d->d_tbad,
-                               nw64);
-            HIP_OK(hipGetLastError());
-        }
-        HIP_OK(hipMemGetInfo(&free_b, &total_b));
-        if (n * 60 + need < free_b / 10 * 9) {
-            HIP_OK(hipMalloc(&sa, n * 4));
-            try {
-                HIP_OK(hipStreamSynchronize(d->stream));
-                const char* inj = std::getenv("SPEQ_INJECT_SA_SORT_FAILURE");
-                if (inj && inj[0] == '1') throw DeviceError("build_ax: injected suffix-sort failure");
-                gpu_suffix_sort(d->d_text, (uint32_t)n, sa, d->stream, false);
-                HIP_OK(hipStreamSynchronize(d->stream));
-            } catch (const std::exception&) {
-                (void)hipStreamSynchronize(d->stream);
-                (void)hipGetLastError();
-                (void)hipFree(sa);
-                sa = nullptr;  // first claimants represent their k-mers
-            }
-        }
-        alloc(&ax.gran, gran_bytes);
-        HIP_OK(hipMalloc(&owner, (n + 1) * 4));
-        HIP_OK(hipMalloc(&codes, n + 64));
-        HIP_OK(hipMalloc(&d_cnt, 8));
-        HIP_OK(hipMemsetAsync(owner, 0xFF, (n + 1) * 4, d->stream));
-        HIP_OK(hipMemsetAsync(d_cnt, 0, 8, d->stream));
-        const DevView v = search_view(d, k);
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 16384);
-        hipLaunchKernelGGL(k_ax_classify, dim3(grid), dim3(256), 0, d->stream, v, d->d_text, d->d_tbad, n, k, codes,
-                           owner, sa, d_cnt);
+    const char* who = "build_ax";
+    DevPtr<uint64_t> text2, tbad;  // the replica adopts the pair, and the table's three arrays, only when complete
+    DevPtr<> gran, filt, atab;
+    DevPtr<uint32_t> owner, sa;
+    DevPtr<uint8_t> codes;
+    DevPtr<unsigned long long> d_cnt;
+    SyncOnExit sync(d->stream);  // after the buffers: whatever was enqueued has ended before one of them is freed
+    if (!d->d_text2) {  // 2-bit text + non-ACGT bitmap, once per replica
+        text2 = DevPtr<uint64_t>::alloc(nw64 * 2, who);
+        tbad = DevPtr<uint64_t>::alloc(nw64, who);
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((nw64 + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_ax_text2, dim3(grid), dim3(256), 0, d->stream, d->d_text, n, text2.get(), tbad.get(), nw64);
         HIP_OK(hipGetLastError());
-        const uint32_t pgrid = (uint32_t)std::min<uint64_t>((n_gran + 255) / 256, 16384);
-        hipLaunchKernelGGL(k_ax_pack, dim3(pgrid), dim3(256), 0, d->stream, d->d_text2, 2 * nw64, codes, n,
-                           reinterpret_cast<u32x4*>(ax.gran), n_gran);
-        HIP_OK(hipGetLastError());
-        unsigned long long distinct = 0;
-        HIP_OK(hipMemcpyAsync(&distinct, d_cnt, 8, hipMemcpyDeviceToHost, d->stream));
-        HIP_OK(hipStreamSynchronize(d->stream));
-        if (sa) {  // read by k_ax_classify only
-            (void)hipFree(sa);
-            sa = nullptr;
-        }
-        ax.distinct = distinct;
-        const uint32_t load = ax_effective_load(d);
-        ax.nf = std::max<uint64_t>(1, distinct * AX_FILTER_BITS / 64);
-        ax.nb = std::max<uint64_t>(1, (uint64_t)((double)distinct * 100.0 / (8.0 * load)) + 1);
-        // the m-mer filter (k_ax_mfilter) after the buckets: 16 bits per m-mer, sized by the distinct k-mers plus
-        // the m-mers that start no valid k-mer window near a text end (k per text); an undersized filter only
-        // passes more m-mers (their windows are deferred as before), it never proves a present window absent
-        ax.m = ax_mproof_m(n, k);
-        ax.nmf = ax.m ? std::max<uint64_t>(1, (distinct + (uint64_t)d->n_texts * k) * AX_FILTER_BITS / 64) : 0;
-        if (ax.m && ax.nb * 64u + ax.nmf * 8u + 16u >= (1ull << 32) - 64) ax.m = 0, ax.nmf = 0;
-        if (ax.nb * 64u >= (1ull << 32) - 64 || ax.nf * 8 >= (1ull << 32) - 64) {
-            // the scan addresses the tables with 32-bit buffer offsets: leave this k to the other kernels
-            cleanup();
-            for (void* q : mine) (void)hipFree(q);
-            return AxTable{};
-        }
-        // the substitution bitmap S (k_ax_sbitmap, filled by ensure_ax_sproof) after the m-mer filter: 1 bit per text
-        // position in whole blocks of 256, + 16 B of load slack; all zero (no proofs) until it is filled
-        ax.s_off = ax.nb * 64u + (ax.m ? ax.nmf * 8u + 16u : 0u);
-        ax.s_words = SPEQ_AX_SPROOF ? ((n + 255) / 256) * 4 : 0;
-        if (ax.s_off + ax.s_words * 8u + 16u >= (1ull << 32) - 64) ax.s_words = 0;
-        const uint64_t s_bytes = ax.s_words ? ax.s_words * 8u + 16u : 0u;
-        HIP_OK(hipMemGetInfo(&free_b, &total_b));
-        const uint64_t atab_bytes = ax.s_off + s_bytes;
-        if (atab_bytes + ax.nf * 8 > free_b / 10 * 9) {  // the table and filters do not fit now: try again later
-            cleanup();
-            for (void* q : mine) (void)hipFree(q);
-            AxTable t;
-            t.transient = true;
-            return t;
-        }
-        alloc(&ax.filt, ax.nf * 8);
-        HIP_OK(hipMemsetAsync(ax.filt, 0, ax.nf * 8, d->stream));
-        alloc(&ax.atab, atab_bytes);
-        HIP_OK(hipMemsetAsync(ax.atab, 0xFF, ax.nb * 64u, d->stream));
-        if (s_bytes) HIP_OK(hipMemsetAsync(static_cast<char*>(ax.atab) + ax.s_off, 0, s_bytes, d->stream));
-        if (ax.m) {
-            unsigned long long* mf = reinterpret_cast<unsigned long long*>(static_cast<char*>(ax.atab) + ax.nb * 64u);
-            HIP_OK(hipMemsetAsync(mf, 0, ax.nmf * 8u + 16u, d->stream));
-            hipLaunchKernelGGL(k_ax_mfilter, dim3(grid), dim3(256), 0, d->stream, d->d_text2, d->d_tbad, n, ax.m, mf,
-                               ax.nmf);
-            HIP_OK(hipGetLastError());
-        }
-        hipLaunchKernelGGL(k_ax_insert, dim3(grid), dim3(256), 0, d->stream, owner, n, d->d_text2, k, d->d_text_start,
-                           d->d_text_group, d->n_texts, reinterpret_cast<unsigned long long*>(ax.atab), ax.nb,
-                           reinterpret_cast<unsigned long long*>(ax.filt), ax.nf);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipStreamSynchronize(d->stream));
-        ax.load = load;
-        ax.gran_bytes = gran_bytes;
-        ax.bytes = atab_bytes + ax.nf * 8 + gran_bytes;
-        ax.ok = true;
-    } catch (...) {
-        cleanup();
-        for (void* q : mine) (void)hipFree(q);
-        throw;
+        d->allocs.reserve(d->allocs.size() + 2);  // so that neither adoption can throw: both arrays, or none
+        d->d_tbad = d->adopt(std::move(tbad));
+        d->d_text2 = d->adopt(std::move(text2));
     }
-    cleanup();
-    for (void* q : mine) d->track(q);
+    HIP_OK(hipMemGetInfo(&free_b, &total_b));
+    if (n * 60 + need < free_b / 10 * 9) {
+        sa = DevPtr<uint32_t>::alloc(n, who);
+        try {
+            HIP_OK(hipStreamSynchronize(d->stream));
+            const char* inj = std::getenv("SPEQ_INJECT_SA_SORT_FAILURE");
+            if (inj && inj[0] == '1') throw DeviceError("build_ax: injected suffix-sort failure");
+            gpu_suffix_sort(d->d_text, (uint32_t)n, sa.get(), d->stream, false);
+            HIP_OK(hipStreamSynchronize(d->stream));
+        } catch (const std::exception&) {  // not a cleanup: the build goes on without the suffix array
+            (void)hipStreamSynchronize(d->stream);
+            (void)hipGetLastError();
+            sa.reset();  // first claimants represent their k-mers
+        }
+    }
+    gran = DevPtr<>::alloc(gran_bytes, who);
+    owner = DevPtr<uint32_t>::alloc(n + 1, who);
+    codes = DevPtr<uint8_t>::alloc(n + 64, who);
+    d_cnt = DevPtr<unsigned long long>::alloc(1, who);
+    HIP_OK(hipMemsetAsync(owner.get(), 0xFF, (n + 1) * 4, d->stream));
+    HIP_OK(hipMemsetAsync(d_cnt.get(), 0, 8, d->stream));
+    const DevView v = search_view(d, k);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 16384);
+    hipLaunchKernelGGL(k_ax_classify, dim3(grid), dim3(256), 0, d->stream, v, d->d_text, d->d_tbad, n, k, codes.get(),
+                       owner.get(), sa.get(), d_cnt.get());
+    HIP_OK(hipGetLastError());
+    const uint32_t pgrid = (uint32_t)std::min<uint64_t>((n_gran + 255) / 256, 16384);
+    hipLaunchKernelGGL(k_ax_pack, dim3(pgrid), dim3(256), 0, d->stream, d->d_text2, 2 * nw64, codes.get(), n,
+                       reinterpret_cast<u32x4*>(gran.get()), n_gran);
+    HIP_OK(hipGetLastError());
+    unsigned long long distinct = 0;
+    HIP_OK(hipMemcpyAsync(&distinct, d_cnt.get(), 8, hipMemcpyDeviceToHost, d->stream));
+    HIP_OK(hipStreamSynchronize(d->stream));
+    sa.reset();  // read by k_ax_classify only
+    ax.distinct = distinct;
+    const uint32_t load = ax_effective_load(d);
+    ax.nf = std::max<uint64_t>(1, distinct * AX_FILTER_BITS / 64);
+    ax.nb = std::max<uint64_t>(1, (uint64_t)((double)distinct * 100.0 / (8.0 * load)) + 1);
+    // the m-mer filter (k_ax_mfilter) after the buckets: 16 bits per m-mer, sized by the distinct k-mers plus
+    // the m-mers that start no valid k-mer window near a text end (k per text); an undersized filter only
+    // passes more m-mers (their windows are deferred as before), it never proves a present window absent
+    ax.m = ax_mproof_m(n, k);
+    ax.nmf = ax.m ? std::max<uint64_t>(1, (distinct + (uint64_t)d->n_texts * k) * AX_FILTER_BITS / 64) : 0;
+    if (ax.m && ax.nb * 64u + ax.nmf * 8u + 16u >= (1ull << 32) - 64) ax.m = 0, ax.nmf = 0;
+    // the scan addresses the tables with 32-bit buffer offsets: leave this k to the other kernels
+    if (ax.nb * 64u >= (1ull << 32) - 64 || ax.nf * 8 >= (1ull << 32) - 64) return AxTable{};
+    // the substitution bitmap S (k_ax_sbitmap, filled by ensure_ax_sproof) after the m-mer filter: 1 bit per text
+    // position in whole blocks of 256, + 16 B of load slack; all zero (no proofs) until it is filled
+    ax.s_off = ax.nb * 64u + (ax.m ? ax.nmf * 8u + 16u : 0u);
+    ax.s_words = SPEQ_AX_SPROOF ? ((n + 255) / 256) * 4 : 0;
+    if (ax.s_off + ax.s_words * 8u + 16u >= (1ull << 32) - 64) ax.s_words = 0;
+    const uint64_t s_bytes = ax.s_words ? ax.s_words * 8u + 16u : 0u;
+    HIP_OK(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t atab_bytes = ax.s_off + s_bytes;
+    if (atab_bytes + ax.nf * 8 > free_b / 10 * 9) {  // the table and filters do not fit now: try again later
+        AxTable t;
+        t.transient = true;
+        return t;
+    }
+    filt = DevPtr<>::alloc(ax.nf * 8, who);
+    HIP_OK(hipMemsetAsync(filt.get(), 0, ax.nf * 8, d->stream));
+    atab = DevPtr<>::alloc(atab_bytes, who);
+    HIP_OK(hipMemsetAsync(atab.get(), 0xFF, ax.nb * 64u, d->stream));
+    if (s_bytes) HIP_OK(hipMemsetAsync(static_cast<char*>(atab.get()) + ax.s_off, 0, s_bytes, d->stream));
+    if (ax.m) {
+        unsigned long long* mf = reinterpret_cast<unsigned long long*>(static_cast<char*>(atab.get()) + ax.nb * 64u);
+        HIP_OK(hipMemsetAsync(mf, 0, ax.nmf * 8u + 16u, d->stream));
+        hipLaunchKernelGGL(k_ax_mfilter, dim3(grid), dim3(256), 0, d->stream, d->d_text2, d->d_tbad, n, ax.m, mf,
+                           ax.nmf);
+        HIP_OK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_ax_insert, dim3(grid), dim3(256), 0, d->stream, owner.get(), n, d->d_text2, k, d->d_text_start,
+                       d->d_text_group, d->n_texts, reinterpret_cast<unsigned long long*>(atab.get()), ax.nb,
+                       reinterpret_cast<unsigned long long*>(filt.get()), ax.nf);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(d->stream));
+    ax.load = load;
+    ax.gran_bytes = gran_bytes;
+    ax.bytes = atab_bytes + ax.nf * 8 + gran_bytes;
+    d->allocs.reserve(d->allocs.size() + 3);
+    ax.gran = d->adopt(std::move(gran));  // complete: the replica takes the three arrays
+    ax.filt = d->adopt(std::move(filt));
+    ax.atab = d->adopt(std::move(atab));
+    ax.ok = true;
     ax.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     startup_trace("per-k structures built");
     return ax;
@@ -1952,23 +1928,18 @@ static bool ensure_ax_em(speq_device_index* d, AxTable* ax, uint32_t k) {
     size_t free_b = 0, total_b = 0;
     HIP_OK(hipMemGetInfo(&free_b, &total_b));
     if ((n + 64) * 8 > free_b / 10 * 9) return false;
-    uint32_t* mlo = nullptr;
-    uint32_t* mhi = nullptr;
-    HIP_OK(hipMalloc(&mlo, (n + 64) * 4));
-    if (hipMalloc(&mhi, (n + 64) * 4) != hipSuccess) {
-        (void)hipFree(mlo);
-        throw DeviceError("ensure_ax_em: hipMalloc failed");
-    }
+    DevPtr<uint32_t> mlo = DevPtr<uint32_t>::alloc(n + 64, "ensure_ax_em");
+    DevPtr<uint32_t> mhi = DevPtr<uint32_t>::alloc(n + 64, "ensure_ax_em");
+    SyncOnExit sync(d->stream);
     const DevView v = search_view(d, k);
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 16384);
     hipLaunchKernelGGL(k_ax_em_intervals, dim3(grid), dim3(256), 0, d->stream, v, d->d_text,
-                       reinterpret_cast<const u32x4*>(ax->gran), n, k, mlo, mhi);
+                       reinterpret_cast<const u32x4*>(ax->gran), n, k, mlo.get(), mhi.get());
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(d->stream));
-    d->track(mlo);
-    d->track(mhi);
-    ax->mhi = mhi;
-    ax->mlo = mlo;  // last: the unlocked check in ax_facts reads it
+    d->allocs.reserve(d->allocs.size() + 2);
+    ax->mhi = d->adopt(std::move(mhi));
+    ax->mlo = d->adopt(std::move(mlo));  // last: the unlocked check in ax_facts reads it
     ax->bytes += (n + 64) * 8;
     return true;
 }

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "fm_index.hpp"
+#include "scan_device.hpp"
 #include "speq_errors.hpp"
 
 namespace speq {
@@ -202,31 +203,14 @@ __global__ void k_lab(const uint16_t* __restrict__ label, const uint32_t* __rest
 
 inline uint32_t grid(uint64_t n, uint32_t bs = 256) { return (uint32_t)((n + bs - 1) / bs); }
 
+using speq_dev::DevPtr;
+using speq_dev::DevTemp;
+using speq_dev::SyncOnExit;
+constexpr const char* WHO = "gpu build";
 template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    explicit DevBuf(uint64_t count) { BHIP(hipMalloc(&p, std::max<uint64_t>(count, 1) * sizeof(T))); }
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-};
-
-struct Temp {
-    void* p = nullptr;
-    size_t bytes = 0;
-    void need(size_t b) {
-        if (b <= bytes) return;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        BHIP(hipMalloc(&p, b));
-        bytes = b;
-    }
-    ~Temp() {
-        if (p) (void)hipFree(p);
-    }
-};
+DevPtr<T> dev(uint64_t count) {
+    return DevPtr<T>::alloc(count, WHO);
+}
 
 uint32_t bits_for(uint64_t v) {
     uint32_t b = 1;
@@ -241,20 +225,22 @@ uint32_t bits_for(uint64_t v) {
 // Used by the index build below and by the anchor-structure build (ax_scan.hip: median representatives).
 void gpu_suffix_sort(const uint8_t* d_text, uint32_t n, uint32_t* d_sa, void* stream, bool timing) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    DevBuf<uint32_t> d_rank(n);
-    Temp tmp;
+    const DevPtr<uint32_t> d_rank = dev<uint32_t>(n);
+    DevTemp tmp;
     {
-        DevBuf<uint64_t> k0(n), k1(n);
-        DevBuf<uint32_t> v0(n), v1(n), head(n), keep(n), off(n), pos0(n), pos1(n), suf0(n);
+        const DevPtr<uint64_t> k0 = dev<uint64_t>(n), k1 = dev<uint64_t>(n);
+        const DevPtr<uint32_t> v0 = dev<uint32_t>(n), v1 = dev<uint32_t>(n), head = dev<uint32_t>(n),
+                               keep = dev<uint32_t>(n), off = dev<uint32_t>(n), pos0 = dev<uint32_t>(n),
+                               pos1 = dev<uint32_t>(n), suf0 = dev<uint32_t>(n);
+        SyncOnExit sync(st);  // (a throw: the rounds enqueued so far have ended before their buffers go)
         // round 0
-        k_init_keys<<<grid(n), 256, 0, st>>>(d_text, n, k0.p, v0.p);
+        k_init_keys<<<grid(n), 256, 0, st>>>(d_text, n, k0.get(), v0.get());
         BHIP(hipGetLastError());
-        rocprim::double_buffer<uint64_t> kb(k0.p, k1.p);
-        rocprim::double_buffer<uint32_t> vb(v0.p, v1.p);
+        rocprim::double_buffer<uint64_t> kb(k0.get(), k1.get());
+        rocprim::double_buffer<uint32_t> vb(v0.get(), v1.get());
         size_t need = 0;
         BHIP(rocprim::radix_sort_pairs(nullptr, need, kb, vb, n, 0, 3 * KEY_SYMS, st));
-        tmp.need(need);
-        BHIP(rocprim::radix_sort_pairs(tmp.p, need, kb, vb, n, 0, 3 * KEY_SYMS, st));
+        BHIP(rocprim::radix_sort_pairs(tmp.need(need, WHO), need, kb, vb, n, 0, 3 * KEY_SYMS, st));
         uint32_t m = n;
         const uint32_t* cur_pos = nullptr;  // SA slots of the active list; nullptr = identity (round 0)
         uint32_t h = KEY_SYMS;
@@ -263,37 +249,36 @@ void gpu_suffix_sort(const uint8_t* d_text, uint32_t n, uint32_t* d_sa, void* st
         for (;;) {
             ++rounds;
             // groups of equal keys in the sorted active list: head slot by max-scan, ranks, survivors
-            k_heads<<<grid(m), 256, 0, st>>>(kb.current(), m, head.p);
+            k_heads<<<grid(m), 256, 0, st>>>(kb.current(), m, head.get());
             BHIP(hipGetLastError());
-            BHIP(rocprim::inclusive_scan(nullptr, need, head.p, head.p, m, rocprim::maximum<uint32_t>(), st));
-            tmp.need(need);
-            BHIP(rocprim::inclusive_scan(tmp.p, need, head.p, head.p, m, rocprim::maximum<uint32_t>(), st));
-            k_assign<<<grid(m), 256, 0, st>>>(kb.current(), vb.current(), head.p, cur_pos, m, d_sa, d_rank.p,
-                                              keep.p);
+            BHIP(rocprim::inclusive_scan(nullptr, need, head.get(), head.get(), m, rocprim::maximum<uint32_t>(), st));
+            BHIP(rocprim::inclusive_scan(tmp.need(need, WHO), need, head.get(), head.get(), m,
+                                         rocprim::maximum<uint32_t>(), st));
+            k_assign<<<grid(m), 256, 0, st>>>(kb.current(), vb.current(), head.get(), cur_pos, m, d_sa, d_rank.get(),
+                                              keep.get());
             BHIP(hipGetLastError());
-            BHIP(rocprim::exclusive_scan(nullptr, need, keep.p, off.p, 0u, m, rocprim::plus<uint32_t>(), st));
-            tmp.need(need);
-            BHIP(rocprim::exclusive_scan(tmp.p, need, keep.p, off.p, 0u, m, rocprim::plus<uint32_t>(), st));
+            BHIP(rocprim::exclusive_scan(nullptr, need, keep.get(), off.get(), 0u, m, rocprim::plus<uint32_t>(), st));
+            BHIP(rocprim::exclusive_scan(tmp.need(need, WHO), need, keep.get(), off.get(), 0u, m,
+                                         rocprim::plus<uint32_t>(), st));
             uint32_t last_off = 0, last_keep = 0;
             // on st: the caller's stream may be a non-blocking one (the replica's), which hipMemcpy does not wait for
-            BHIP(hipMemcpyAsync(&last_off, off.p + (m - 1), 4, hipMemcpyDeviceToHost, st));
-            BHIP(hipMemcpyAsync(&last_keep, keep.p + (m - 1), 4, hipMemcpyDeviceToHost, st));
+            BHIP(hipMemcpyAsync(&last_off, off.get() + (m - 1), 4, hipMemcpyDeviceToHost, st));
+            BHIP(hipMemcpyAsync(&last_keep, keep.get() + (m - 1), 4, hipMemcpyDeviceToHost, st));
             BHIP(hipStreamSynchronize(st));
             const uint32_t m2 = last_off + last_keep;
             if (m2 == 0) break;
             if (h >= n) throw std::runtime_error("gpu build: suffix sorting did not converge");
             // compact the survivors: slots alternate between two buffers (the current ones are being read)
-            uint32_t* npos = cur_pos == pos0.p ? pos1.p : pos0.p;
-            k_compact<<<grid(m), 256, 0, st>>>(keep.p, off.p, cur_pos, vb.current(), m, npos, suf0.p);
+            uint32_t* npos = cur_pos == pos0.get() ? pos1.get() : pos0.get();
+            k_compact<<<grid(m), 256, 0, st>>>(keep.get(), off.get(), cur_pos, vb.current(), m, npos, suf0.get());
             BHIP(hipGetLastError());
             m = m2;
             cur_pos = npos;
             // next round: sort the survivors by (rank[s], rank[s + h]), i.e. by their first 2h symbols
-            k_pair_keys<<<grid(m), 256, 0, st>>>(suf0.p, m, d_rank.p, n, h, rb, kb.current(), vb.current());
+            k_pair_keys<<<grid(m), 256, 0, st>>>(suf0.get(), m, d_rank.get(), n, h, rb, kb.current(), vb.current());
             BHIP(hipGetLastError());
             BHIP(rocprim::radix_sort_pairs(nullptr, need, kb, vb, m, 0, 2 * rb, st));
-            tmp.need(need);
-            BHIP(rocprim::radix_sort_pairs(tmp.p, need, kb, vb, m, 0, 2 * rb, st));
+            BHIP(rocprim::radix_sort_pairs(tmp.need(need, WHO), need, kb, vb, m, 0, 2 * rb, st));
             h *= 2;
         }
         if (timing) std::fprintf(stderr, "fm_build[gpu]: %u doubling rounds\n", rounds);
@@ -328,55 +313,62 @@ void fm_build_arrays_gpu(FmIndex& idx, int device, bool pair_steps, bool triple_
     const uint32_t n = (uint32_t)n64;
     const uint32_t nb = (uint32_t)idx.n_blocks();
 
-    DevBuf<uint8_t> d_text(n);
-    BHIP(hipMemcpy(d_text.p, idx.text.data(), n, hipMemcpyHostToDevice));
-    DevBuf<uint32_t> d_sa(n);
-    gpu_suffix_sort(d_text.p, n, d_sa.p, st, timing);
-    Temp tmp;  // rocPRIM scratch of the steps below
+    const DevPtr<uint8_t> d_text = dev<uint8_t>(n);
+    BHIP(hipMemcpy(d_text.get(), idx.text.data(), n, hipMemcpyHostToDevice));
+    const DevPtr<uint32_t> d_sa = dev<uint32_t>(n);
+    gpu_suffix_sort(d_text.get(), n, d_sa.get(), st, timing);
+    DevTemp tmp;  // rocPRIM scratch of the steps below
     phase("sa");
 
     idx.sa.resize(n);
-    BHIP(hipMemcpy(idx.sa.data(), d_sa.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    BHIP(hipMemcpy(idx.sa.data(), d_sa.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
 
-    DevBuf<uint64_t> d_ts(idx.text_start.size());
-    DevBuf<int32_t> d_tg(idx.text_group.size());
-    BHIP(hipMemcpy(d_ts.p, idx.text_start.data(), idx.text_start.size() * 8, hipMemcpyHostToDevice));
-    BHIP(hipMemcpy(d_tg.p, idx.text_group.data(), idx.text_group.size() * 4, hipMemcpyHostToDevice));
-    DevBuf<uint8_t> d_bwt(n), d_bwt2(n), d_code3(triple_steps ? n : 1);
-    DevBuf<uint16_t> d_label(n);
-    k_bwt<<<grid(n), 256, 0, st>>>(d_text.p, d_sa.p, n, d_ts.p, idx.n_texts, d_tg.p, d_bwt.p, d_bwt2.p,
-                                   triple_steps ? d_code3.p : nullptr, d_label.p);
+    const DevPtr<uint64_t> d_ts = dev<uint64_t>(idx.text_start.size());
+    const DevPtr<int32_t> d_tg = dev<int32_t>(idx.text_group.size());
+    BHIP(hipMemcpy(d_ts.get(), idx.text_start.data(), idx.text_start.size() * 8, hipMemcpyHostToDevice));
+    BHIP(hipMemcpy(d_tg.get(), idx.text_group.data(), idx.text_group.size() * 4, hipMemcpyHostToDevice));
+    const DevPtr<uint8_t> d_bwt = dev<uint8_t>(n), d_bwt2 = dev<uint8_t>(n),
+                          d_code3 = dev<uint8_t>(triple_steps ? n : 1);
+    const DevPtr<uint16_t> d_label = dev<uint16_t>(n);
+    SyncOnExit sync(st);  // (a throw: the steps enqueued so far have ended before a buffer goes; so the guards below)
+    k_bwt<<<grid(n), 256, 0, st>>>(d_text.get(), d_sa.get(), n, d_ts.get(), idx.n_texts, d_tg.get(), d_bwt.get(),
+                                   d_bwt2.get(), triple_steps ? d_code3.get() : nullptr, d_label.get());
     BHIP(hipGetLastError());
 
     // planes: bitmaps + popcounts, one exclusive scan per plane, counts = scan + base (C[s] / C2[ab] / 0)
     auto build_planes = [&](int kind, uint32_t n_planes, const std::vector<uint32_t>& base,
                             std::vector<OccEntry>& out) {
         const uint64_t total = (uint64_t)nb * n_planes;
-        DevBuf<OccEntry> d_pl(total);
-        DevBuf<uint32_t> d_pop(total), d_ex(total), d_base(n_planes);
+        const DevPtr<OccEntry> d_pl = dev<OccEntry>(total);
+        const DevPtr<uint32_t> d_pop = dev<uint32_t>(total), d_ex = dev<uint32_t>(total),
+                               d_base = dev<uint32_t>(n_planes);
+        SyncOnExit sync_planes(st);
         const uint32_t g = grid(total);
         if (kind == PK_OCC)
-            k_planes<PK_OCC><<<g, 256, 0, st>>>(d_bwt.p, d_bwt2.p, d_label.p, n, nb, n_planes, d_pl.p, d_pop.p);
+            k_planes<PK_OCC><<<g, 256, 0, st>>>(d_bwt.get(), d_bwt2.get(), d_label.get(), n, nb, n_planes, d_pl.get(),
+                                                d_pop.get());
         else if (kind == PK_OCC2)
-            k_planes<PK_OCC2><<<g, 256, 0, st>>>(d_bwt.p, d_bwt2.p, d_label.p, n, nb, n_planes, d_pl.p, d_pop.p);
+            k_planes<PK_OCC2><<<g, 256, 0, st>>>(d_bwt.get(), d_bwt2.get(), d_label.get(), n, nb, n_planes, d_pl.get(),
+                                                 d_pop.get());
         else if (kind == PK_OCC3)
-            k_planes<PK_OCC3><<<g, 256, 0, st>>>(d_bwt.p, d_code3.p, d_label.p, n, nb, n_planes, d_pl.p, d_pop.p);
+            k_planes<PK_OCC3><<<g, 256, 0, st>>>(d_bwt.get(), d_code3.get(), d_label.get(), n, nb, n_planes, d_pl.get(),
+                                                 d_pop.get());
         else
-            k_planes<PK_RUNS><<<g, 256, 0, st>>>(d_bwt.p, d_bwt2.p, d_label.p, n, nb, n_planes, d_pl.p, d_pop.p);
+            k_planes<PK_RUNS><<<g, 256, 0, st>>>(d_bwt.get(), d_bwt2.get(), d_label.get(), n, nb, n_planes, d_pl.get(),
+                                                 d_pop.get());
         BHIP(hipGetLastError());
         for (uint32_t pl = 0; pl < n_planes; ++pl) {
             size_t need = 0;
-            BHIP(rocprim::exclusive_scan(nullptr, need, d_pop.p + (uint64_t)pl * nb, d_ex.p + (uint64_t)pl * nb, 0u,
-                                         nb, rocprim::plus<uint32_t>(), st));
-            tmp.need(need);
-            BHIP(rocprim::exclusive_scan(tmp.p, need, d_pop.p + (uint64_t)pl * nb, d_ex.p + (uint64_t)pl * nb, 0u,
-                                         nb, rocprim::plus<uint32_t>(), st));
+            BHIP(rocprim::exclusive_scan(nullptr, need, d_pop.get() + (uint64_t)pl * nb, d_ex.get() + (uint64_t)pl * nb,
+                                         0u, nb, rocprim::plus<uint32_t>(), st));
+            BHIP(rocprim::exclusive_scan(tmp.need(need, WHO), need, d_pop.get() + (uint64_t)pl * nb,
+                                         d_ex.get() + (uint64_t)pl * nb, 0u, nb, rocprim::plus<uint32_t>(), st));
         }
-        BHIP(hipMemcpy(d_base.p, base.data(), n_planes * 4, hipMemcpyHostToDevice));
-        k_fold_counts<<<g, 256, 0, st>>>(d_pl.p, d_ex.p, total, nb, d_base.p);
+        BHIP(hipMemcpy(d_base.get(), base.data(), n_planes * 4, hipMemcpyHostToDevice));
+        k_fold_counts<<<g, 256, 0, st>>>(d_pl.get(), d_ex.get(), total, nb, d_base.get());
         BHIP(hipGetLastError());
         out.resize(total);
-        BHIP(hipMemcpy(out.data(), d_pl.p, total * sizeof(OccEntry), hipMemcpyDeviceToHost));
+        BHIP(hipMemcpy(out.data(), d_pl.get(), total * sizeof(OccEntry), hipMemcpyDeviceToHost));
     };
     {
         std::vector<uint32_t> base(5);
@@ -411,29 +403,32 @@ void fm_build_arrays_gpu(FmIndex& idx, int device, bool pair_steps, bool triple_
     phase("occ3");
     build_planes(PK_RUNS, 1, std::vector<uint32_t>(1, 0u), idx.runs);
     {
-        DevBuf<uint32_t> flag(n), run_id(n);
-        k_run_flags<<<grid(n), 256, 0, st>>>(d_label.p, n, flag.p);
+        const DevPtr<uint32_t> flag = dev<uint32_t>(n), run_id = dev<uint32_t>(n);
+        SyncOnExit sync_runs(st);
+        k_run_flags<<<grid(n), 256, 0, st>>>(d_label.get(), n, flag.get());
         BHIP(hipGetLastError());
         size_t need = 0;
-        BHIP(rocprim::inclusive_scan(nullptr, need, flag.p, run_id.p, n, rocprim::plus<uint32_t>(), st));
-        tmp.need(need);
-        BHIP(rocprim::inclusive_scan(tmp.p, need, flag.p, run_id.p, n, rocprim::plus<uint32_t>(), st));
+        BHIP(rocprim::inclusive_scan(nullptr, need, flag.get(), run_id.get(), n, rocprim::plus<uint32_t>(), st));
+        BHIP(rocprim::inclusive_scan(tmp.need(need, WHO), need, flag.get(), run_id.get(), n,
+                                     rocprim::plus<uint32_t>(), st));
         uint32_t last = 0;
-        BHIP(hipMemcpy(&last, run_id.p + (n - 1), 4, hipMemcpyDeviceToHost));
+        BHIP(hipMemcpy(&last, run_id.get() + (n - 1), 4, hipMemcpyDeviceToHost));
         const uint32_t n_runs = last + 1;
-        DevBuf<uint32_t> starts(n_runs + 1);
-        DevBuf<uint16_t> rl(n_runs);
-        k_run_starts<<<grid(n), 256, 0, st>>>(flag.p, run_id.p, n, d_label.p, starts.p, rl.p);
+        const DevPtr<uint32_t> starts = dev<uint32_t>(n_runs + 1);
+        const DevPtr<uint16_t> rl = dev<uint16_t>(n_runs);
+        SyncOnExit sync_starts(st);
+        k_run_starts<<<grid(n), 256, 0, st>>>(flag.get(), run_id.get(), n, d_label.get(), starts.get(), rl.get());
         BHIP(hipGetLastError());
-        BHIP(hipMemcpy(starts.p + n_runs, &n, 4, hipMemcpyHostToDevice));
+        BHIP(hipMemcpy(starts.get() + n_runs, &n, 4, hipMemcpyHostToDevice));
         idx.run_label.resize(n_runs);
-        BHIP(hipMemcpy(idx.run_label.data(), rl.p, (size_t)n_runs * 2, hipMemcpyDeviceToHost));
+        BHIP(hipMemcpy(idx.run_label.data(), rl.get(), (size_t)n_runs * 2, hipMemcpyDeviceToHost));
         if (label_table) {
-            DevBuf<uint32_t> lab(n);
-            k_lab<<<grid(n), 256, 0, st>>>(d_label.p, run_id.p, starts.p, n, lab.p);
+            const DevPtr<uint32_t> lab = dev<uint32_t>(n);
+            SyncOnExit sync_lab(st);
+            k_lab<<<grid(n), 256, 0, st>>>(d_label.get(), run_id.get(), starts.get(), n, lab.get());
             BHIP(hipGetLastError());
             idx.lab.resize(n);
-            BHIP(hipMemcpy(idx.lab.data(), lab.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+            BHIP(hipMemcpy(idx.lab.data(), lab.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
         } else {
             idx.lab.clear();
         }

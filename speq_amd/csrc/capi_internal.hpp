@@ -3,6 +3,7 @@
 #include <new>
 #include <string>
 
+#include "dev_mem.hpp"
 #include "fm_index.hpp"
 #include "speq_errors.hpp"
 #include "speq_scan.h"
@@ -43,6 +44,21 @@ int guarded(F&& f) {
         set_last_error(e.what());
         return SPEQ_E_ARG;
     }
+}
+
+// guarded() with a device allocation's failure as SPEQ_E_NOMEM (guarded() keeps its message as a DeviceError's)
+template <typename F>
+int guarded_nomem(F&& f) {
+    bool nomem = false;
+    const int rc = guarded([&] {
+        try {
+            f();
+        } catch (const speq_dev::OutOfDeviceMemory&) {
+            nomem = true;
+            throw;
+        }
+    });
+    return nomem ? SPEQ_E_NOMEM : rc;
 }
 
 }  // namespace speq

@@ -420,17 +420,16 @@ int speq_allreduce_host(void* comm, int device, void* buf, uint64_t count, int i
         int prev = 0;
         if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(device) != hipSuccess)
             throw speq::DeviceError("speq_allreduce_host: cannot select GPU " + std::to_string(device));
-        void* d = nullptr;
-        struct Release {
+        struct Restore {
             int dev;
-            void*& p;
-            ~Release() {
-                if (p) (void)hipFree(p);
-                (void)hipSetDevice(dev);
-            }
-        } release{prev, d};
+            ~Restore() { (void)hipSetDevice(dev); }
+        } restore{prev};
         const size_t bytes = (size_t)count * 8;
-        if (hipMalloc(&d, bytes) != hipSuccess) throw speq::DeviceError("speq_allreduce_host: hipMalloc failed");
+        const speq_dev::DevPtr<> owner = speq_dev::DevPtr<>::alloc(bytes, "speq_allreduce_host");
+        struct Wait {  // the reduction runs on the null stream: it has ended before the buffer goes
+            ~Wait() { (void)hipStreamSynchronize(nullptr); }
+        } wait;
+        void* d = owner.get();
         if (hipMemcpy(d, buf, bytes, hipMemcpyHostToDevice) != hipSuccess)
             throw speq::DeviceError("speq_allreduce_host: copy to the device failed");
         nccl_ok(rccl().all_reduce(d, d, count, is_f64 ? ncclFloat64 : ncclUint64, ncclSum, c->nccl, nullptr),
@@ -456,17 +455,17 @@ int speq_em_allreduce(speq_em* em, void* comm, void* stream) {
         if (c->transport == SPEQ_COMM_RCCL) {
             // interval ends are 0 wherever a rank never wrote (speq_em_create / em_clear zero them), so the max is
             // the interval end wherever any rank saw the interval start
-            nccl_ok(rccl().all_reduce(em->d_mult, em->d_mult, em->n, ncclUint32, ncclSum, c->nccl, st),
+            nccl_ok(rccl().all_reduce(em->d_mult.get(), em->d_mult.get(), em->n, ncclUint32, ncclSum, c->nccl, st),
                     "ncclAllReduce");
-            nccl_ok(rccl().all_reduce(em->d_hi, em->d_hi, em->n, ncclUint32, ncclMax, c->nccl, st), "ncclAllReduce");
+            nccl_ok(rccl().all_reduce(em->d_hi.get(), em->d_hi.get(), em->n, ncclUint32, ncclMax, c->nccl, st), "ncclAllReduce");
             if (hipStreamSynchronize(st) != hipSuccess) throw speq::DeviceError("speq_em_allreduce: stream failed");
             return;
         }
         // host sockets: the nonzero positions travel as {position, multiplicity, interval end} triples
         if (hipStreamSynchronize(st) != hipSuccess) throw speq::DeviceError("speq_em_allreduce: stream failed");
         std::vector<uint32_t> mult(em->n), hi(em->n);
-        if (hipMemcpy(mult.data(), em->d_mult, em->n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(hi.data(), em->d_hi, em->n * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        if (hipMemcpy(mult.data(), em->d_mult.get(), em->n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(hi.data(), em->d_hi.get(), em->n * 4, hipMemcpyDeviceToHost) != hipSuccess)
             throw speq::DeviceError("speq_em_allreduce: copy to the host failed");
         if (c->nranks > 1) {
             auto pack = [&] {
@@ -514,8 +513,8 @@ int speq_em_allreduce(speq_em* em, void* comm, void* stream) {
                 }
             }
         }
-        if (hipMemcpy(em->d_mult, mult.data(), em->n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(em->d_hi, hi.data(), em->n * 4, hipMemcpyHostToDevice) != hipSuccess)
+        if (hipMemcpy(em->d_mult.get(), mult.data(), em->n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(em->d_hi.get(), hi.data(), em->n * 4, hipMemcpyHostToDevice) != hipSuccess)
             throw speq::DeviceError("speq_em_allreduce: copy to the device failed");
     });
 }

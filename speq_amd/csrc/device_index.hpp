@@ -18,7 +18,8 @@ struct AxView;  // ax_common.hpp
 using speq_dev::DevView;
 
 namespace speq {
-// Per-k structures of the anchor-and-extend scan (ax_scan.hip).
+// Per-k structures of the anchor-and-extend scan (ax_scan.hip). The pointers do not own: the replica
+// adopts the arrays when the table is complete (build_ax, ensure_ax_em) and frees them when it closes.
 struct AxTable {
     void* gran = nullptr;      // per 32 text positions {2-bit text, class plane 0, class plane 1} (see ax_scan.hip)
     uint32_t* mlo = nullptr;   // SA interval start of the multi-group k-mer at a text position (EM scans only: built
@@ -46,11 +47,12 @@ struct AxTable {
 struct speq_device_index {
     int device = 0;
     DevView view{};
-    std::vector<void*> allocs;  // every device allocation of the replica, freed by the destructor
-    template <typename T>
-    T* track(T* p) {
-        if (p) allocs.push_back((void*)p);
-        return p;
+    std::vector<speq_dev::DevPtr<>> allocs;  // every device allocation of the replica, freed by the destructor
+    template <class T>
+    T* adopt(speq_dev::DevPtr<T>&& p) {  // the replica owns p's memory from here on (null: nothing)
+        T* raw = p.get();
+        if (raw) allocs.emplace_back(std::move(p));
+        return raw;
     }
     ~speq_device_index();
     uint8_t* d_text = nullptr;
@@ -92,7 +94,7 @@ struct speq_device_index {
     uint32_t kt_load8 = 35;       // tuning "kt_load8": load factor of compact tables, percent (35-42 best at cfg 2,
                                   // sweep_kt_load8_sgpr.jsonl)
     uint32_t kt_slots = 2;        // tuning "kt_slots": table slots per distinct k-mer (load factor 1/kt_slots .. 2/kt_slots)
-    struct KmerTable {
+    struct KmerTable {  // the pointers do not own: the replica adopts a complete table's arrays (build_ktab)
         uint4* table = nullptr;
         uint64_t buckets = 0, distinct = 0;
         double build_ms = 0.0;

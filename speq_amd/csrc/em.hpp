@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "dev_mem.hpp"
 
 struct speq_device_index;
 
@@ -19,8 +20,8 @@ struct speq_em {
     speq_device_index* dev = nullptr;
     uint64_t n = 0;      // SA positions
     uint32_t G = 0;
-    uint32_t* d_mult = nullptr;  // device: per SA position, # multi-group windows whose interval starts there
-    uint32_t* d_hi = nullptr;    // device: end of that interval
+    speq_dev::DevPtr<uint32_t> d_mult;  // device: per SA position, # multi-group windows whose interval starts there
+    speq_dev::DevPtr<uint32_t> d_hi;    // device: end of that interval
     bool finalized = false;
     uint64_t n_intervals = 0;  // distinct multi-group intervals recorded (rows before equal rows are merged)
     uint64_t n_entries = 0;    // their (group, count) entries

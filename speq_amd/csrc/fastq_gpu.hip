@@ -460,13 +460,6 @@ void launch_fastq_parse(const uint8_t* d_raw, uint64_t len1, uint64_t len2, uint
 
 namespace speq {
 namespace {
-struct DevBuf {  // device allocation of at least one byte, freed on scope exit
-    uint8_t* p = nullptr;
-    explicit DevBuf(size_t n) { FHIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 16))); }
-    ~DevBuf() { (void)hipFree(p); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-};
 struct DevSelect {  // hipSetDevice for the scope
     int prev = 0;
     explicit DevSelect(int device) {
@@ -500,28 +493,35 @@ extern "C" int speq_fastq_parse_block(int device, const uint8_t* raw, uint64_t l
         const uint64_t raw_cap = align16(len) + 16;
         const size_t scratch_bytes = fastq_gpu_scratch_bytes(std::max(len1, len2), n_records, paired != 0);
         DevSelect g(device);
-        DevBuf d_raw(raw_cap), d_scratch(scratch_bytes), d_seq(len), d_qual(len), d_off((n_slots + 1) * 8), d_misc(32);
-        FHIP(hipMemset(d_raw.p + len, pad_byte, raw_cap - len));
-        if (len) FHIP(hipMemcpy(d_raw.p, raw, len, hipMemcpyHostToDevice));
-        FHIP(hipMemset(d_scratch.p, poison, scratch_bytes));
-        FHIP(hipMemset(d_off.p, poison, (n_slots + 1) * 8));
+        const char* who = "speq_fastq_parse_block";
+        using Buf = speq_dev::DevPtr<uint8_t>;
+        const Buf d_raw = Buf::alloc(raw_cap, who), d_scratch = Buf::alloc(scratch_bytes, who),
+                  d_seq = Buf::alloc(len, who), d_qual = Buf::alloc(len, who), d_off = Buf::alloc((n_slots + 1) * 8, who),
+                  d_misc = Buf::alloc(32, who);
+        struct Wait {  // the parse runs on the null stream: a throw waits for it before the buffers go
+            ~Wait() { (void)hipDeviceSynchronize(); }
+        } wait;
+        FHIP(hipMemset(d_raw.get() + len, pad_byte, raw_cap - len));
+        if (len) FHIP(hipMemcpy(d_raw.get(), raw, len, hipMemcpyHostToDevice));
+        FHIP(hipMemset(d_scratch.get(), poison, scratch_bytes));
+        FHIP(hipMemset(d_off.get(), poison, (n_slots + 1) * 8));
         if (len) {
-            FHIP(hipMemset(d_seq.p, poison, len));
-            FHIP(hipMemset(d_qual.p, poison, len));
+            FHIP(hipMemset(d_seq.get(), poison, len));
+            FHIP(hipMemset(d_qual.get(), poison, len));
         }
-        FHIP(hipMemset(d_misc.p, 0, 32));  // [0, 4) the error flags, [16, 24) the base total
+        FHIP(hipMemset(d_misc.get(), 0, 32));  // [0, 4) the error flags, [16, 24) the base total
         FHIP(hipDeviceSynchronize());
-        launch_fastq_parse(d_raw.p, len1, len2, n_records, paired != 0, d_scratch.p, scratch_bytes, d_seq.p, d_qual.p,
-                           reinterpret_cast<uint64_t*>(d_off.p), reinterpret_cast<uint32_t*>(d_misc.p),
-                           reinterpret_cast<uint64_t*>(d_misc.p + 16), nullptr);
+        launch_fastq_parse(d_raw.get(), len1, len2, n_records, paired != 0, d_scratch.get(), scratch_bytes, d_seq.get(),
+                           d_qual.get(), reinterpret_cast<uint64_t*>(d_off.get()), reinterpret_cast<uint32_t*>(d_misc.get()),
+                           reinterpret_cast<uint64_t*>(d_misc.get() + 16), nullptr);
         FHIP(hipDeviceSynchronize());
         if (len) {
-            FHIP(hipMemcpy(seq, d_seq.p, len, hipMemcpyDeviceToHost));
-            FHIP(hipMemcpy(qual, d_qual.p, len, hipMemcpyDeviceToHost));
+            FHIP(hipMemcpy(seq, d_seq.get(), len, hipMemcpyDeviceToHost));
+            FHIP(hipMemcpy(qual, d_qual.get(), len, hipMemcpyDeviceToHost));
         }
-        FHIP(hipMemcpy(offsets, d_off.p, (n_slots + 1) * 8, hipMemcpyDeviceToHost));
-        FHIP(hipMemcpy(err, d_misc.p, 4, hipMemcpyDeviceToHost));
-        FHIP(hipMemcpy(total_bases, d_misc.p + 16, 8, hipMemcpyDeviceToHost));
+        FHIP(hipMemcpy(offsets, d_off.get(), (n_slots + 1) * 8, hipMemcpyDeviceToHost));
+        FHIP(hipMemcpy(err, d_misc.get(), 4, hipMemcpyDeviceToHost));
+        FHIP(hipMemcpy(total_bases, d_misc.get() + 16, 8, hipMemcpyDeviceToHost));
     });
 }
 

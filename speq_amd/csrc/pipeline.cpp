@@ -396,7 +396,7 @@ int speq_pipeline_submit(speq_pipeline* pl, int32_t slot, uint64_t n_records) {
         hipStream_t cs = pl->lane();
         hip_ok(hipStreamWaitEvent(cs, s.copied, 0), "hipStreamWaitEvent");
         speq::launch_reads_scan(pl->d, s.d_seq, s.d_qual, s.d_off, n_records, &pl->p, pl->d_counts, pl->d_w,
-                                pl->em ? pl->em->d_mult : nullptr, pl->em ? pl->em->d_hi : nullptr, cs);
+                                pl->em ? pl->em->d_mult.get() : nullptr, pl->em ? pl->em->d_hi.get() : nullptr, cs);
         hip_ok(hipEventRecord(s.done, cs), "hipEventRecord");
         s.pending = true;
     });
@@ -458,7 +458,7 @@ void pipeline_submit_raw(speq_pipeline* pl, int32_t slot, uint64_t len1, uint64_
     launch_fastq_parse(s.d_seq, len1, len2, n, paired, s.d_scratch, s.scratch_bytes, s.d_pseq, s.d_pqual, s.d_poff,
                        pl->d_err, pl->d_bases, cs);
     launch_reads_scan(pl->d, s.d_pseq, s.d_pqual, s.d_poff, n_slots, &pl->p, pl->d_counts, pl->d_w,
-                      pl->em ? pl->em->d_mult : nullptr, pl->em ? pl->em->d_hi : nullptr, cs);
+                      pl->em ? pl->em->d_mult.get() : nullptr, pl->em ? pl->em->d_hi.get() : nullptr, cs);
     hip_ok(hipEventRecord(s.done, cs), "hipEventRecord");
     s.pending = true;
 }
@@ -734,7 +734,7 @@ void pipeline_submit_packed_impl(speq_pipeline* pl, int32_t slot, uint64_t n_rec
         launch_unpack_bases(s.d_seq, bytes, s.d_pseq, s.d_pqual, cs);
     }
     launch_reads_scan(pl->d, s.d_pseq, s.d_pqual, s.d_off, n_records, &pl->p, pl->d_counts, pl->d_w,
-                      pl->em ? pl->em->d_mult : nullptr, pl->em ? pl->em->d_hi : nullptr, cs);
+                      pl->em ? pl->em->d_mult.get() : nullptr, pl->em ? pl->em->d_hi.get() : nullptr, cs);
     hip_ok(hipEventRecord(s.done, cs), "hipEventRecord");
     s.pending = true;
 }

@@ -27,8 +27,8 @@ struct speq_bootstrap {
     uint64_t seed = 0;
     // accumulators with the replicates contiguous: counts cell (c, b) at c * R + b for c < G + 2, weights cell (g, b)
     // at g * R + b (the 64 lanes of a wave add to consecutive addresses); finalize transposes them on the host
-    unsigned long long* d_counts = nullptr;
-    double* d_weights = nullptr;  // local mode only
+    speq_dev::DevPtr<unsigned long long> d_counts;
+    speq_dev::DevPtr<double> d_weights;  // local mode only
     std::atomic<uint32_t> lds_path{0};
     std::atomic<uint64_t> units_added{0};
     // an attached EM histogram (speq_bootstrap_attach_em): the sorted interval starts with the slot of
@@ -36,10 +36,8 @@ struct speq_bootstrap {
     bool em_attached = false;
     uint64_t em_rows = 0;
     uint32_t em_m = 0, em_lds_rows = 0;
-    uint32_t* d_em_lo = nullptr;
-    uint32_t* d_em_slot = nullptr;
-    unsigned long long* d_em_mult = nullptr;
-    unsigned long long* d_em_missed = nullptr;
+    speq_dev::DevPtr<uint32_t> d_em_lo, d_em_slot;
+    speq_dev::DevPtr<unsigned long long> d_em_mult, d_em_missed;
     std::vector<uint32_t> em_slot_of_row;
 };
 
@@ -261,21 +259,6 @@ Kernel pick(bool paired, bool local, bool lds, bool em) {
     return local ? pick<false, true>(lds, em) : pick<false, false>(lds, em);
 }
 
-// guarded() with the device allocations' failure as SPEQ_E_NOMEM (as speq_markers_*)
-template <typename F>
-int guarded_nomem(F&& f) {
-    bool nomem = false;
-    const int rc = speq::guarded([&] {
-        try {
-            f();
-        } catch (const OutOfDeviceMemory&) {
-            nomem = true;
-            throw;
-        }
-    });
-    return nomem ? SPEQ_E_NOMEM : rc;
-}
-
 void check_create_args(const char* who, const speq_scan_params* p, uint32_t replicates) {
     if (!p) throw std::invalid_argument(std::string(who) + ": null params");
     speq::check_report_k(who, p->k);
@@ -301,18 +284,13 @@ void create_impl(speq_device_index* d, const speq_scan_params* p, uint32_t repli
     b->seed = seed;
     const uint64_t R = (uint64_t)replicates + 1u;
     const size_t cb = (size_t)(R * (b->G + 2u) * 8u), wb = (size_t)(R * b->G * 8u);
-    dev_alloc(reinterpret_cast<void**>(&b->d_counts), cb, who);
-    try {
-        if (is_local(*p)) dev_alloc(reinterpret_cast<void**>(&b->d_weights), wb, who);
-        HIP_OK(hipMemsetAsync(b->d_counts, 0, cb, d->stream));
-        if (b->d_weights) HIP_OK(hipMemsetAsync(b->d_weights, 0, std::max<size_t>(wb, 16), d->stream));
-        // the adds come on the callers' streams: the zeros are in place before the handle exists
-        HIP_OK(hipStreamSynchronize(d->stream));
-    } catch (...) {
-        (void)hipFree(b->d_counts);
-        if (b->d_weights) (void)hipFree(b->d_weights);
-        throw;
-    }
+    b->d_counts = DevPtr<unsigned long long>::alloc(cb / 8u, who);
+    if (is_local(*p)) b->d_weights = DevPtr<double>::alloc(wb / 8u, who);
+    SyncOnExit sync(d->stream);  // (declared after b: the stream is idle before a throw frees the handle's arrays)
+    HIP_OK(hipMemsetAsync(b->d_counts.get(), 0, cb, d->stream));
+    if (b->d_weights) HIP_OK(hipMemsetAsync(b->d_weights.get(), 0, std::max<size_t>(wb, 16), d->stream));
+    // the adds come on the callers' streams: the zeros are in place before the handle exists
+    HIP_OK(hipStreamSynchronize(d->stream));
     *out = b.release();
 }
 
@@ -331,7 +309,8 @@ void add_device_impl(speq_bootstrap* b, const uint8_t* d_seq, const uint8_t* d_q
     const uint32_t k = b->params.k, R = b->B + 1u;
     const bool local = is_local(b->params), lds_acc = fits_lds(R, b->G, local, k);
     const DevView v = speq::search_view(d, k);
-    const EmDev E{b->d_em_lo, b->d_em_slot, b->d_em_mult, b->d_em_missed, b->em_m, b->em_lds_rows};
+    const EmDev E{b->d_em_lo.get(), b->d_em_slot.get(), b->d_em_mult.get(), b->d_em_missed.get(),
+                  b->em_m, b->em_lds_rows};
     const size_t lds = (size_t)WAVES_PER_BLOCK * wave_bytes(k) + (lds_acc ? (size_t)acc_bytes(R, b->G, local) : 0) +
                        (size_t)E.lds_rows * R * 8u;
     // LDS path (the counters', or an attached histogram's hot rows alone): a block zeroes and flushes its accumulators
@@ -342,7 +321,7 @@ void add_device_impl(speq_bootstrap* b, const uint8_t* d_seq, const uint8_t* d_q
     const uint64_t blocks = std::min<uint64_t>(want, lds_grid ? per_cu * std::max(d->n_cus, 1u) : 16384u);
     hipLaunchKernelGGL(pick(paired, local, lds_acc, b->em_attached), dim3((uint32_t)blocks), dim3(BLOCK_THREADS), lds,
                        st, v, d_seq, d_qual, d_offsets, n_units, first_unit, k, b->params.phred_cutoff, R, b->seed,
-                       d->d_qlut, b->d_counts, b->d_weights, E);
+                       d->d_qlut, b->d_counts.get(), b->d_weights.get(), E);
     HIP_OK(hipGetLastError());
     b->lds_path = lds_acc ? 1u : 0u;
     b->units_added += n_units;
@@ -378,27 +357,18 @@ void finalize_impl(speq_bootstrap* b, uint64_t* counts, double* weights) {
     HIP_OK(hipDeviceSynchronize());  // the adds of every stream of the device have completed
     const uint32_t R = b->B + 1u, G = b->G, C = G + 2u;
     std::vector<uint64_t> hc((size_t)R * C);
-    HIP_OK(hipMemcpy(hc.data(), b->d_counts, hc.size() * 8, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(hc.data(), b->d_counts.get(), hc.size() * 8, hipMemcpyDeviceToHost));
     for (uint32_t c = 0; c < C; ++c)
         for (uint32_t r = 0; r < R; ++r) counts[(size_t)r * C + c] = hc[(size_t)c * R + r];
     if (local && G) {
         std::vector<double> hw((size_t)R * G);
-        HIP_OK(hipMemcpy(hw.data(), b->d_weights, hw.size() * 8, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(hw.data(), b->d_weights.get(), hw.size() * 8, hipMemcpyDeviceToHost));
         for (uint32_t c = 0; c < G; ++c)
             for (uint32_t r = 0; r < R; ++r) weights[(size_t)r * G + c] = hw[(size_t)c * R + r];
     }
 }
 
 // ---- an attached EM histogram ----
-void free_em(speq_bootstrap* b) {
-    if (b->d_em_lo) (void)hipFree(b->d_em_lo);
-    if (b->d_em_slot) (void)hipFree(b->d_em_slot);
-    if (b->d_em_mult) (void)hipFree(b->d_em_mult);
-    if (b->d_em_missed) (void)hipFree(b->d_em_missed);
-    b->d_em_lo = b->d_em_slot = nullptr;
-    b->d_em_mult = b->d_em_missed = nullptr;
-}
-
 void attach_em_impl(speq_bootstrap* b, const speq_em* em) {
     const char* who = "speq_bootstrap_attach_em";
     if (!b || !em) throw std::invalid_argument(std::string(who) + ": null argument");
@@ -421,23 +391,24 @@ void attach_em_impl(speq_bootstrap* b, const speq_em* em) {
     for (uint64_t s = 0; s < n_rows; ++s) slot_of_row[order[s]] = (uint32_t)s;
     for (uint64_t i = 0; i < m; ++i) slot[i] = slot_of_row[em->iv_row[i]];
     const size_t mb = (size_t)(n_rows * R * 8u);
-    try {
-        dev_alloc(reinterpret_cast<void**>(&b->d_em_lo), m * 4u, who);
-        dev_alloc(reinterpret_cast<void**>(&b->d_em_slot), m * 4u, who);
-        dev_alloc(reinterpret_cast<void**>(&b->d_em_mult), mb, who);
-        dev_alloc(reinterpret_cast<void**>(&b->d_em_missed), 8, who);
+    // (the handle takes the four arrays when they are filled: a failure leaves it without a histogram)
+    DevPtr<uint32_t> lo = DevPtr<uint32_t>::alloc(m, who), sl = DevPtr<uint32_t>::alloc(m, who);
+    DevPtr<unsigned long long> mult = DevPtr<unsigned long long>::alloc(mb / 8u, who);
+    DevPtr<unsigned long long> missed = DevPtr<unsigned long long>::alloc(1, who);
+    {
+        SyncOnExit sync(d->stream);
         if (m) {
-            HIP_OK(hipMemcpyAsync(b->d_em_lo, em->iv_lo.data(), m * 4u, hipMemcpyHostToDevice, d->stream));
-            HIP_OK(hipMemcpyAsync(b->d_em_slot, slot.data(), m * 4u, hipMemcpyHostToDevice, d->stream));
+            HIP_OK(hipMemcpyAsync(lo.get(), em->iv_lo.data(), m * 4u, hipMemcpyHostToDevice, d->stream));
+            HIP_OK(hipMemcpyAsync(sl.get(), slot.data(), m * 4u, hipMemcpyHostToDevice, d->stream));
         }
-        HIP_OK(hipMemsetAsync(b->d_em_mult, 0, std::max<size_t>(mb, 16), d->stream));
-        HIP_OK(hipMemsetAsync(b->d_em_missed, 0, 8, d->stream));
+        HIP_OK(hipMemsetAsync(mult.get(), 0, std::max<size_t>(mb, 16), d->stream));
+        HIP_OK(hipMemsetAsync(missed.get(), 0, 8, d->stream));
         HIP_OK(hipStreamSynchronize(d->stream));  // (the host vectors above are read until here)
-    } catch (...) {
-        (void)hipStreamSynchronize(d->stream);
-        free_em(b);
-        throw;
     }
+    b->d_em_lo = std::move(lo);
+    b->d_em_slot = std::move(sl);
+    b->d_em_mult = std::move(mult);
+    b->d_em_missed = std::move(missed);
     b->em_rows = n_rows;
     b->em_m = (uint32_t)m;
     b->em_lds_rows = em_lds_rows(n_rows, R, b->G, is_local(b->params), b->params.k);
@@ -455,12 +426,12 @@ void finalize_em_impl(speq_bootstrap* b, uint64_t* mult, uint64_t* missed) {
     HIP_OK(hipDeviceSynchronize());  // the adds of every stream of the device have completed
     const uint64_t R = b->B + 1u, n_rows = b->em_rows;
     std::vector<uint64_t> hm((size_t)(n_rows * R));
-    if (n_rows) HIP_OK(hipMemcpy(hm.data(), b->d_em_mult, hm.size() * 8, hipMemcpyDeviceToHost));
+    if (n_rows) HIP_OK(hipMemcpy(hm.data(), b->d_em_mult.get(), hm.size() * 8, hipMemcpyDeviceToHost));
     for (uint64_t row = 0; row < n_rows; ++row) {
         const uint64_t* cells = hm.data() + (uint64_t)b->em_slot_of_row[row] * R;
         for (uint64_t r = 0; r < R; ++r) mult[r * n_rows + row] = cells[r];
     }
-    if (missed) HIP_OK(hipMemcpy(missed, b->d_em_missed, 8, hipMemcpyDeviceToHost));
+    if (missed) HIP_OK(hipMemcpy(missed, b->d_em_missed.get(), 8, hipMemcpyDeviceToHost));
 }
 
 // ---- the summary (host only) ----
@@ -541,22 +512,22 @@ extern "C" {
 
 int speq_bootstrap_create(speq_device_index* d, const speq_scan_params* params, uint32_t replicates, uint64_t seed,
                           speq_bootstrap** out) {
-    return guarded_nomem([&] { create_impl(d, params, replicates, seed, out); });
+    return speq::guarded_nomem([&] { create_impl(d, params, replicates, seed, out); });
 }
 
 int speq_bootstrap_add_reads_device(speq_bootstrap* b, const uint8_t* d_seq, const uint8_t* d_qual,
                                     const uint64_t* d_offsets, uint64_t n_reads, uint64_t first_unit, void* stream) {
-    return guarded_nomem(
+    return speq::guarded_nomem(
         [&] { add_device_impl(b, d_seq, d_qual, d_offsets, n_reads, first_unit, static_cast<hipStream_t>(stream)); });
 }
 
 int speq_bootstrap_add_reads(speq_bootstrap* b, const uint8_t* seq, const uint8_t* qual, const uint64_t* offsets,
                              uint64_t n_reads, uint64_t first_unit) {
-    return guarded_nomem([&] { add_host_impl(b, seq, qual, offsets, n_reads, first_unit); });
+    return speq::guarded_nomem([&] { add_host_impl(b, seq, qual, offsets, n_reads, first_unit); });
 }
 
 int speq_bootstrap_finalize(speq_bootstrap* b, uint64_t* counts, double* weights) {
-    return guarded_nomem([&] { finalize_impl(b, counts, weights); });
+    return speq::guarded_nomem([&] { finalize_impl(b, counts, weights); });
 }
 
 int speq_bootstrap_info(const speq_bootstrap* b, uint32_t* replicates, uint32_t* lds_path, uint64_t* units_added) {
@@ -568,16 +539,10 @@ int speq_bootstrap_info(const speq_bootstrap* b, uint32_t* replicates, uint32_t*
     });
 }
 
-void speq_bootstrap_free(speq_bootstrap* b) {
-    if (!b) return;
-    if (b->d_counts) (void)hipFree(b->d_counts);
-    if (b->d_weights) (void)hipFree(b->d_weights);
-    free_em(b);
-    delete b;
-}
+void speq_bootstrap_free(speq_bootstrap* b) { delete b; }
 
 int speq_bootstrap_attach_em(speq_bootstrap* b, const speq_em* em) {
-    return guarded_nomem([&] { attach_em_impl(b, em); });
+    return speq::guarded_nomem([&] { attach_em_impl(b, em); });
 }
 
 int speq_bootstrap_em_info(const speq_bootstrap* b, uint64_t* n_rows, uint32_t* lds_rows) {
@@ -590,7 +555,7 @@ int speq_bootstrap_em_info(const speq_bootstrap* b, uint64_t* n_rows, uint32_t* 
 }
 
 int speq_bootstrap_finalize_em(speq_bootstrap* b, uint64_t* mult, uint64_t* missed) {
-    return guarded_nomem([&] { finalize_em_impl(b, mult, missed); });
+    return speq::guarded_nomem([&] { finalize_em_impl(b, mult, missed); });
 }
 
 int speq_bootstrap_summary_percent(const double* percent, const double* estimate, const uint8_t* used_mask,

@@ -39,13 +39,16 @@ struct speq_dedup {
     speq_device_index* dev = nullptr;
     bool paired = false;
     std::mutex mu;                      // everything below
-    std::vector<unsigned char*> chunks;  // chunk c holds the units c * CHUNK ..; null: not reached yet
+    std::vector<speq_dev::DevPtr<unsigned char>> chunks;  // chunk c holds the units c * CHUNK ..; null: not reached yet
     hipStream_t zero_stream = nullptr;  // the zeroing of a new chunk's seen words, waited for before the chunk is used
     uint64_t units_added = 0, end_unit = 0;  // units of every add; one past the highest unit added
     bool finalized = false;             // a finalize succeeded and no add came after it
     uint64_t n = 0;                     // units of that finalize
-    uint32_t* d_rep = nullptr;          // [rep_cap]: rep[u] of that finalize
+    speq_dev::DevPtr<uint32_t> d_rep;   // [rep_cap]: rep[u] of that finalize
     uint64_t rep_cap = 0;
+    ~speq_dedup() {
+        if (zero_stream) (void)hipStreamDestroy(zero_stream);
+    }
 };
 
 namespace {
@@ -195,21 +198,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_dedup_mask(uint8_t* __restric
     }
 }
 
-// guarded() with the device allocations' failure as SPEQ_E_NOMEM (as speq_markers_*)
-template <typename F>
-int guarded_nomem(F&& f) {
-    bool nomem = false;
-    const int rc = speq::guarded([&] {
-        try {
-            f();
-        } catch (const OutOfDeviceMemory&) {
-            nomem = true;
-            throw;
-        }
-    });
-    return nomem ? SPEQ_E_NOMEM : rc;
-}
-
 inline uint32_t grid1d(uint64_t n) { return (uint32_t)((n + 255u) / 256u); }
 // blocks of four waves, one wave per item, striding past the cap
 inline uint32_t wave_grid(uint64_t items) {
@@ -231,20 +219,16 @@ void create_impl(speq_device_index* d, uint32_t paired, speq_dedup** out) {
 // the chunk of unit u, allocated and its seen words zeroed on first use (h->mu held)
 unsigned char* chunk_for(speq_dedup* h, uint64_t u, const char* who) {
     const size_t c = (size_t)(u >> CHUNK_LOG);
-    if (h->chunks.size() <= c) h->chunks.resize(c + 1, nullptr);
+    if (h->chunks.size() <= c) h->chunks.resize(c + 1);
     if (!h->chunks[c]) {
-        void* p = nullptr;
-        dev_alloc(&p, CHUNK_BYTES, who);
+        DevPtr<unsigned char> p = DevPtr<unsigned char>::alloc(CHUNK_BYTES, who);
+        SyncOnExit sync(h->zero_stream);
         // the adds come on the callers' streams: the zeros are in place before any of them can reach the chunk
-        hipError_t e = hipMemsetAsync(static_cast<unsigned char*>(p) + 16u * CHUNK, 0, 4u * CHUNK, h->zero_stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->zero_stream);
-        if (e != hipSuccess) {
-            (void)hipFree(p);
-            HIP_OK(e);
-        }
-        h->chunks[c] = static_cast<unsigned char*>(p);
+        HIP_OK(hipMemsetAsync(p.get() + 16u * CHUNK, 0, 4u * CHUNK, h->zero_stream));
+        HIP_OK(hipStreamSynchronize(h->zero_stream));
+        h->chunks[c] = std::move(p);
     }
-    return h->chunks[c];
+    return h->chunks[c].get();
 }
 
 void check_units(const char* who, const speq_dedup* h, uint64_t n_reads, uint64_t first_unit) {
@@ -306,20 +290,6 @@ void add_host_impl(speq_dedup* h, const uint8_t* seq, const uint64_t* offsets, u
                        });
 }
 
-struct Temp {  // rocprim's temporary storage, grown as asked
-    void* p = nullptr;
-    size_t cap = 0;
-    ~Temp() { (void)hipFree(p); }
-    void need(size_t bytes, const char* who) {
-        if (bytes <= cap) return;
-        (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        dev_alloc(&p, bytes, who);
-        cap = bytes;
-    }
-};
-
 void finalize_impl(speq_dedup* h, speq_dedup_stats* out) {
     const char* who = "speq_dedup_finalize";
     if (!h) throw std::invalid_argument(std::string(who) + ": null handle");
@@ -339,45 +309,47 @@ void finalize_impl(speq_dedup* h, speq_dedup_stats* out) {
         const uint32_t n = (uint32_t)N;
         hipStream_t st = d->stream;
         if (h->rep_cap < N) {
-            if (h->d_rep) (void)hipFree(h->d_rep);
-            h->d_rep = nullptr;
+            h->d_rep.reset();  // first, so that the two are never alive together
             h->rep_cap = 0;
-            dev_alloc(reinterpret_cast<void**>(&h->d_rep), N * 4u, who);
+            h->d_rep = DevPtr<uint32_t>::alloc(N, who);
             h->rep_cap = N;
         }
-        DevBuf tbl(n_chunks * sizeof(void*), who), k0(N * 8u, who), k1(N * 8u, who), v0(N * 4u, who), v1(N * 4u, who),
-            head(N * 4u, who), dst(12u * 8u, who);
-        Temp tmp;
-        const unsigned char* const* T = static_cast<const unsigned char* const*>(tbl.p);
-        unsigned long long* d_stats = static_cast<unsigned long long*>(dst.p);  // [3] counts the units not added once
-        HIP_OK(hipMemcpyAsync(tbl.p, h->chunks.data(), n_chunks * sizeof(void*), hipMemcpyHostToDevice, st));
+        std::vector<const unsigned char*> table(n_chunks);  // the chunks' addresses, for the kernels
+        for (size_t c = 0; c < n_chunks; ++c) table[c] = h->chunks[c].get();
+        const DevPtr<const unsigned char*> tbl = DevPtr<const unsigned char*>::alloc(n_chunks, who);
+        const DevPtr<uint64_t> k0 = DevPtr<uint64_t>::alloc(N, who), k1 = DevPtr<uint64_t>::alloc(N, who);
+        const DevPtr<uint32_t> v0 = DevPtr<uint32_t>::alloc(N, who), v1 = DevPtr<uint32_t>::alloc(N, who),
+                               head = DevPtr<uint32_t>::alloc(N, who);
+        const DevPtr<unsigned long long> dst = DevPtr<unsigned long long>::alloc(12, who);
+        DevTemp tmp;  // rocprim's temporary storage
+        SyncOnExit sync(st);
+        const unsigned char* const* T = tbl.get();
+        unsigned long long* d_stats = dst.get();  // [3] counts the units not added once
+        HIP_OK(hipMemcpyAsync(tbl.get(), table.data(), n_chunks * sizeof(void*), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemsetAsync(d_stats, 0, 12u * 8u, st));
-        hipLaunchKernelGGL(k_dedup_keys1, dim3(grid1d(N)), dim3(256), 0, st, T, n, static_cast<uint64_t*>(k0.p),
-                           static_cast<uint32_t*>(v0.p), d_stats + 3);
+        hipLaunchKernelGGL(k_dedup_keys1, dim3(grid1d(N)), dim3(256), 0, st, T, n, k0.get(), v0.get(),
+                           d_stats + 3);
         HIP_OK(hipGetLastError());
         unsigned long long bad = 0;
         HIP_OK(hipMemcpyAsync(&bad, d_stats + 3, 8, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         if (bad != 0) throw std::invalid_argument(std::string(who) + not_once);
         // two stable sorts from the identity, by F1 and then by F0: equal fingerprints end up in ascending unit order
-        rocprim::double_buffer<uint64_t> kb(static_cast<uint64_t*>(k0.p), static_cast<uint64_t*>(k1.p));
-        rocprim::double_buffer<uint32_t> vb(static_cast<uint32_t*>(v0.p), static_cast<uint32_t*>(v1.p));
+        rocprim::double_buffer<uint64_t> kb(k0.get(), k1.get());
+        rocprim::double_buffer<uint32_t> vb(v0.get(), v1.get());
         size_t need = 0;
         HIP_OK(rocprim::radix_sort_pairs(nullptr, need, kb, vb, N, 0, 64, st));
-        tmp.need(need, who);
-        HIP_OK(rocprim::radix_sort_pairs(tmp.p, need, kb, vb, N, 0, 64, st));
+        HIP_OK(rocprim::radix_sort_pairs(tmp.need(need, who), need, kb, vb, N, 0, 64, st));
         hipLaunchKernelGGL(k_dedup_keys2, dim3(grid1d(N)), dim3(256), 0, st, T, n, vb.current(), kb.current());
         HIP_OK(hipGetLastError());
         HIP_OK(rocprim::radix_sort_pairs(nullptr, need, kb, vb, N, 0, 64, st));
-        tmp.need(need, who);
-        HIP_OK(rocprim::radix_sort_pairs(tmp.p, need, kb, vb, N, 0, 64, st));
-        uint32_t* hd = static_cast<uint32_t*>(head.p);
+        HIP_OK(rocprim::radix_sort_pairs(tmp.need(need, who), need, kb, vb, N, 0, 64, st));
+        uint32_t* hd = head.get();
         hipLaunchKernelGGL(k_dedup_heads, dim3(grid1d(N)), dim3(256), 0, st, T, n, kb.current(), vb.current(), hd);
         HIP_OK(hipGetLastError());
         HIP_OK(rocprim::inclusive_scan(nullptr, need, hd, hd, N, rocprim::maximum<uint32_t>(), st));
-        tmp.need(need, who);
-        HIP_OK(rocprim::inclusive_scan(tmp.p, need, hd, hd, N, rocprim::maximum<uint32_t>(), st));
-        hipLaunchKernelGGL(k_dedup_mark, dim3(grid1d(N)), dim3(256), 0, st, n, vb.current(), hd, h->d_rep, d_stats);
+        HIP_OK(rocprim::inclusive_scan(tmp.need(need, who), need, hd, hd, N, rocprim::maximum<uint32_t>(), st));
+        hipLaunchKernelGGL(k_dedup_mark, dim3(grid1d(N)), dim3(256), 0, st, n, vb.current(), hd, h->d_rep.get(), d_stats);
         HIP_OK(hipGetLastError());
         unsigned long long hs[12];
         HIP_OK(hipMemcpyAsync(hs, d_stats, sizeof hs, hipMemcpyDeviceToHost, st));
@@ -407,7 +379,7 @@ void representatives_impl(speq_dedup* h, uint64_t first_unit, uint64_t n_units, 
     DeviceGuard g(h->dev->device);
     std::lock_guard<std::mutex> lk(h->mu);
     check_range(who, h, first_unit, n_units);
-    if (n_units) HIP_OK(hipMemcpy(rep, h->d_rep + first_unit, n_units * 4u, hipMemcpyDeviceToHost));
+    if (n_units) HIP_OK(hipMemcpy(rep, h->d_rep.get() + first_unit, n_units * 4u, hipMemcpyDeviceToHost));
 }
 
 void mask_device_impl(speq_dedup* h, uint8_t* d_qual, const uint64_t* d_offsets, uint64_t n_reads, uint64_t first_unit,
@@ -422,7 +394,7 @@ void mask_device_impl(speq_dedup* h, uint8_t* d_qual, const uint64_t* d_offsets,
     check_range(who, h, first_unit, n_reads / per);
     if (n_reads == 0) return;
     hipLaunchKernelGGL(k_dedup_mask, dim3(wave_grid(n_reads)), dim3(BLOCK_THREADS), 0, st, d_qual, d_offsets, n_reads,
-                       per, (uint32_t)first_unit, h->d_rep + first_unit);
+                       per, (uint32_t)first_unit, h->d_rep.get() + first_unit);
     HIP_OK(hipGetLastError());
 }
 
@@ -456,11 +428,13 @@ void scan_reads_impl(speq_dedup* h, speq_em* em, const uint8_t* seq, const uint8
     speq_device_index* d = h->dev;
     DeviceGuard g(d->device);
     const uint32_t G = d->G;
-    DevBuf dc((G + 2u) * 8u, who), dw(G * 8u, who);
-    uint64_t* d_counts = static_cast<uint64_t*>(dc.p);
-    double* d_weights = local ? static_cast<double*>(dw.p) : nullptr;
-    HIP_OK(hipMemsetAsync(dc.p, 0, (G + 2u) * 8u, d->stream));
-    HIP_OK(hipMemsetAsync(dw.p, 0, std::max<size_t>(G * 8u, 16), d->stream));
+    const DevPtr<uint64_t> dc = DevPtr<uint64_t>::alloc(G + 2u, who);
+    const DevPtr<double> dw = DevPtr<double>::alloc(G, who);
+    SyncOnExit sync(d->stream);
+    uint64_t* d_counts = dc.get();
+    double* d_weights = local ? dw.get() : nullptr;
+    HIP_OK(hipMemsetAsync(dc.get(), 0, (G + 2u) * 8u, d->stream));
+    HIP_OK(hipMemsetAsync(dw.get(), 0, std::max<size_t>(G * 8u, 16), d->stream));
     // the staged qualities are this call's own copy: the mask goes over them, the caller's arrays are only read
     for_staged_batches(who, d, seq, qual, offsets, n_reads, per,
                        [&](const uint8_t* d_seq, const uint8_t* d_qual, const uint64_t* d_off, uint64_t r0, uint64_t n) {
@@ -471,9 +445,9 @@ void scan_reads_impl(speq_dedup* h, speq_em* em, const uint8_t* seq, const uint8
                                                                 d->stream));
                        });
     std::vector<uint64_t> hc(G + 2u);
-    HIP_OK(hipMemcpyAsync(hc.data(), dc.p, hc.size() * 8u, hipMemcpyDeviceToHost, d->stream));
+    HIP_OK(hipMemcpyAsync(hc.data(), dc.get(), hc.size() * 8u, hipMemcpyDeviceToHost, d->stream));
     std::vector<double> hw(local ? G : 0u);
-    if (local && G) HIP_OK(hipMemcpyAsync(hw.data(), dw.p, G * 8u, hipMemcpyDeviceToHost, d->stream));
+    if (local && G) HIP_OK(hipMemcpyAsync(hw.data(), dw.get(), G * 8u, hipMemcpyDeviceToHost, d->stream));
     HIP_OK(hipStreamSynchronize(d->stream));
     for (uint32_t i = 0; i < G + 2u; ++i) counts[i] += hc[i];
     for (uint32_t i = 0; i < (uint32_t)hw.size(); ++i) weights[i] += hw[i];
@@ -486,21 +460,21 @@ static_assert(sizeof(speq_dedup_stats) == 96, "speq_dedup_stats is twelve u64");
 extern "C" {
 
 int speq_dedup_create(speq_device_index* d, uint32_t paired, speq_dedup** out) {
-    return guarded_nomem([&] { create_impl(d, paired, out); });
+    return speq::guarded_nomem([&] { create_impl(d, paired, out); });
 }
 
 int speq_dedup_add_reads_device(speq_dedup* h, const uint8_t* d_seq, const uint64_t* d_offsets, uint64_t n_reads,
                                 uint64_t first_unit, void* stream) {
-    return guarded_nomem([&] { add_device_impl(h, d_seq, d_offsets, n_reads, first_unit, static_cast<hipStream_t>(stream)); });
+    return speq::guarded_nomem([&] { add_device_impl(h, d_seq, d_offsets, n_reads, first_unit, static_cast<hipStream_t>(stream)); });
 }
 
 int speq_dedup_add_reads(speq_dedup* h, const uint8_t* seq, const uint64_t* offsets, uint64_t n_reads,
                          uint64_t first_unit) {
-    return guarded_nomem([&] { add_host_impl(h, seq, offsets, n_reads, first_unit); });
+    return speq::guarded_nomem([&] { add_host_impl(h, seq, offsets, n_reads, first_unit); });
 }
 
 int speq_dedup_finalize(speq_dedup* h, speq_dedup_stats* out) {
-    return guarded_nomem([&] { finalize_impl(h, out); });
+    return speq::guarded_nomem([&] { finalize_impl(h, out); });
 }
 
 int speq_dedup_representatives(speq_dedup* h, uint64_t first_unit, uint64_t n_units, uint32_t* rep) {
@@ -516,17 +490,10 @@ int speq_dedup_mask_device(speq_dedup* h, uint8_t* d_qual, const uint64_t* d_off
 int speq_dedup_scan_reads(speq_dedup* h, speq_em* em, const uint8_t* seq, const uint8_t* qual, const uint64_t* offsets,
                           uint64_t n_reads, uint64_t first_unit, const speq_scan_params* params, uint64_t* counts,
                           double* weights) {
-    return guarded_nomem([&] { scan_reads_impl(h, em, seq, qual, offsets, n_reads, first_unit, params, counts, weights); });
+    return speq::guarded_nomem([&] { scan_reads_impl(h, em, seq, qual, offsets, n_reads, first_unit, params, counts, weights); });
 }
 
-void speq_dedup_free(speq_dedup* h) {
-    if (!h) return;
-    for (unsigned char* c : h->chunks)
-        if (c) (void)hipFree(c);
-    if (h->d_rep) (void)hipFree(h->d_rep);
-    if (h->zero_stream) (void)hipStreamDestroy(h->zero_stream);
-    delete h;
-}
+void speq_dedup_free(speq_dedup* h) { delete h; }
 
 void speq_dedup_fingerprint(const uint8_t* seq1, uint64_t len1, const uint8_t* seq2, uint64_t len2, uint64_t out[2]) {
     uint64_t f0 = 0, f1 = 0;

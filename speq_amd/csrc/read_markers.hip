@@ -21,7 +21,7 @@ struct speq_markers {
     speq_scan_params params{};  // k and phred_cutoff, fixed at create
     uint64_t n = 0;             // SA positions
     uint32_t G = 0;
-    uint32_t* d_depth = nullptr;  // [n]: MARK | depth
+    speq_dev::DevPtr<uint32_t> d_depth;  // [n]: MARK | depth
 };
 
 namespace {
@@ -34,21 +34,6 @@ constexpr uint32_t COV_WORDS = sizeof(speq_marker_cov) / 8;  // u64 words of one
 // per-block tally of the fold, per group: u64 hits, then u32 {markers, observed, max_depth, bins[8]}
 constexpr uint32_t TALLY_U32 = 3u + SPEQ_MARKER_BINS;
 __host__ __device__ inline uint32_t tally_bytes(uint32_t G) { return G * (8u + 4u * TALLY_U32); }
-
-// guarded() with the device allocations' failure as SPEQ_E_NOMEM (guarded() keeps its message as a DeviceError's)
-template <typename F>
-int guarded_nomem(F&& f) {
-    bool nomem = false;
-    const int rc = speq::guarded([&] {
-        try {
-            f();
-        } catch (const OutOfDeviceMemory&) {
-            nomem = true;
-            throw;
-        }
-    });
-    return nomem ? SPEQ_E_NOMEM : rc;
-}
 
 // Read pass: one wave64 per read, tiles of 64 window starts. A window whose k-mer lies in one group adds 1 to the
 // depth word at its interval start: a no-return atomic, one per lane (adjacent windows have different starts).
@@ -190,24 +175,20 @@ void create_impl(speq_device_index* d, const speq_scan_params* p, speq_markers**
     m->params = *p;
     m->n = d->view.n;
     m->G = d->G;
-    dev_alloc(reinterpret_cast<void**>(&m->d_depth), m->n * 4, "speq_markers_create");
-    try {
-        hipStream_t st = d->stream;
-        HIP_OK(hipMemsetAsync(m->d_depth, 0, m->n * 4, st));
-        const DevView v = speq::search_view(d, p->k);
-        const uint64_t tiles = m->n >= p->k ? (m->n - p->k + 1 + 63) / 64 : 0;
-        if (tiles) {
-            const uint64_t blocks = std::min<uint64_t>((tiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 16384u);
-            hipLaunchKernelGGL(k_marker_texts, dim3((uint32_t)blocks), dim3(BLOCK_THREADS),
-                               (size_t)WAVES_PER_BLOCK * wave_bytes(p->k), st, v, d->d_text, p->k, m->d_depth);
-            HIP_OK(hipGetLastError());
-        }
-        // the adds come on the callers' streams: the marks are complete before the handle exists
-        HIP_OK(hipStreamSynchronize(st));
-    } catch (...) {
-        (void)hipFree(m->d_depth);
-        throw;
+    m->d_depth = DevPtr<uint32_t>::alloc(m->n, "speq_markers_create");
+    hipStream_t st = d->stream;
+    SyncOnExit sync(st);  // (declared after m: the stream is idle before a throw frees the handle's array)
+    HIP_OK(hipMemsetAsync(m->d_depth.get(), 0, m->n * 4, st));
+    const DevView v = speq::search_view(d, p->k);
+    const uint64_t tiles = m->n >= p->k ? (m->n - p->k + 1 + 63) / 64 : 0;
+    if (tiles) {
+        const uint64_t blocks = std::min<uint64_t>((tiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 16384u);
+        hipLaunchKernelGGL(k_marker_texts, dim3((uint32_t)blocks), dim3(BLOCK_THREADS),
+                           (size_t)WAVES_PER_BLOCK * wave_bytes(p->k), st, v, d->d_text, p->k, m->d_depth.get());
+        HIP_OK(hipGetLastError());
     }
+    // the adds come on the callers' streams: the marks are complete before the handle exists
+    HIP_OK(hipStreamSynchronize(st));
     *out = m.release();
 }
 
@@ -224,7 +205,7 @@ void add_device_impl(speq_markers* m, const uint8_t* d_seq, const uint8_t* d_qua
     const uint64_t blocks = std::min<uint64_t>((n_reads + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 16384u);
     hipLaunchKernelGGL(k_marker_reads, dim3((uint32_t)blocks), dim3(BLOCK_THREADS),
                        (size_t)WAVES_PER_BLOCK * wave_bytes(k), st, v, d_seq, d_qual, d_offsets, n_reads, k,
-                       m->params.phred_cutoff, m->d_depth);
+                       m->params.phred_cutoff, m->d_depth.get());
     HIP_OK(hipGetLastError());
 }
 
@@ -252,18 +233,19 @@ void finalize_impl(speq_markers* m, speq_marker_cov* out) {
     DeviceGuard g(d->device);
     HIP_OK(hipDeviceSynchronize());  // the adds of every stream of the device have completed
     const uint32_t G = m->G;
-    DevBuf cov((size_t)G * sizeof(speq_marker_cov), "speq_markers_finalize");
+    const DevPtr<> cov = DevPtr<>::alloc((size_t)G * sizeof(speq_marker_cov), "speq_markers_finalize");
     hipStream_t st = d->stream;
-    HIP_OK(hipMemsetAsync(cov.p, 0, (size_t)G * sizeof(speq_marker_cov), st));
+    SyncOnExit sync(st);
+    HIP_OK(hipMemsetAsync(cov.get(), 0, (size_t)G * sizeof(speq_marker_cov), st));
     const DevView v = speq::search_view(d, m->params.k);
-    auto* o = static_cast<unsigned long long*>(cov.p);
+    auto* o = static_cast<unsigned long long*>(cov.get());
     if (G <= LDS_TALLY_GROUPS)
         hipLaunchKernelGGL(k_marker_fold<true>, dim3(std::min(grid_1d(m->n), 2048u)), dim3(256), tally_bytes(G), st, v,
-                           m->d_depth, o);
+                           m->d_depth.get(), o);
     else
-        hipLaunchKernelGGL(k_marker_fold<false>, dim3(grid_1d(m->n)), dim3(256), 0, st, v, m->d_depth, o);
+        hipLaunchKernelGGL(k_marker_fold<false>, dim3(grid_1d(m->n)), dim3(256), 0, st, v, m->d_depth.get(), o);
     HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(out, cov.p, (size_t)G * sizeof(speq_marker_cov), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(out, cov.get(), (size_t)G * sizeof(speq_marker_cov), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
 }
 
@@ -274,15 +256,16 @@ void list_impl(speq_markers* m, uint64_t* n_markers, uint32_t* lo, uint32_t* gro
     HIP_OK(hipDeviceSynchronize());
     const uint64_t n = m->n;
     std::vector<uint32_t> w(n), grp;
-    HIP_OK(hipMemcpy(w.data(), m->d_depth, n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(w.data(), m->d_depth.get(), n * 4, hipMemcpyDeviceToHost));
     if (group) {
-        DevBuf dg(n * 4, "speq_markers_list");
+        const DevPtr<uint32_t> dg = DevPtr<uint32_t>::alloc(n, "speq_markers_list");
+        SyncOnExit sync(d->stream);
         hipLaunchKernelGGL(k_marker_groups, dim3(grid_1d(n)), dim3(256), 0, d->stream,
-                           speq::search_view(d, m->params.k), m->d_depth, static_cast<uint32_t*>(dg.p));
+                           speq::search_view(d, m->params.k), m->d_depth.get(), dg.get());
         HIP_OK(hipGetLastError());
         HIP_OK(hipStreamSynchronize(d->stream));
         grp.resize(n);
-        HIP_OK(hipMemcpy(grp.data(), dg.p, n * 4, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(grp.data(), dg.get(), n * 4, hipMemcpyDeviceToHost));
     }
     uint64_t c = 0;
     for (uint64_t i = 0; i < n; ++i) {
@@ -302,31 +285,27 @@ static_assert(sizeof(speq_marker_cov) == 96, "speq_marker_cov is twelve u64 word
 extern "C" {
 
 int speq_markers_create(speq_device_index* d, const speq_scan_params* params, speq_markers** out) {
-    return guarded_nomem([&] { create_impl(d, params, out); });
+    return speq::guarded_nomem([&] { create_impl(d, params, out); });
 }
 
 int speq_markers_add_reads_device(speq_markers* m, const uint8_t* d_seq, const uint8_t* d_qual,
                                   const uint64_t* d_offsets, uint64_t n_reads, void* stream) {
-    return guarded_nomem([&] { add_device_impl(m, d_seq, d_qual, d_offsets, n_reads, static_cast<hipStream_t>(stream)); });
+    return speq::guarded_nomem([&] { add_device_impl(m, d_seq, d_qual, d_offsets, n_reads, static_cast<hipStream_t>(stream)); });
 }
 
 int speq_markers_add_reads(speq_markers* m, const uint8_t* seq, const uint8_t* qual, const uint64_t* offsets,
                            uint64_t n_reads) {
-    return guarded_nomem([&] { add_host_impl(m, seq, qual, offsets, n_reads); });
+    return speq::guarded_nomem([&] { add_host_impl(m, seq, qual, offsets, n_reads); });
 }
 
 int speq_markers_finalize(speq_markers* m, speq_marker_cov* out) {
-    return guarded_nomem([&] { finalize_impl(m, out); });
+    return speq::guarded_nomem([&] { finalize_impl(m, out); });
 }
 
 int speq_markers_list(speq_markers* m, uint64_t* n_markers, uint32_t* lo, uint32_t* group, uint32_t* depth) {
-    return guarded_nomem([&] { list_impl(m, n_markers, lo, group, depth); });
+    return speq::guarded_nomem([&] { list_impl(m, n_markers, lo, group, depth); });
 }
 
-void speq_markers_free(speq_markers* m) {
-    if (!m) return;
-    if (m->d_depth) (void)hipFree(m->d_depth);
-    delete m;
-}
+void speq_markers_free(speq_markers* m) { delete m; }
 
 }  // extern "C"

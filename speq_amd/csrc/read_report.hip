@@ -109,14 +109,16 @@ void report_host_impl(speq_device_index* d, const uint8_t* seq, const uint8_t* q
     const uint32_t per = p->paired ? 2u : 1u, W = (uint32_t)SPEQ_SET_WORDS(d->G);
     DeviceGuard g(d->device);
     const uint64_t most = std::min(n_reads, BATCH_RECORDS) / per;  // units of the largest batch
-    DevBuf drep(most * sizeof(speq_read_report), who), dset(most * W * 8, who);
+    // (for_staged_batches waits for its stream before it leaves, by a throw too: the two outlive every batch's work)
+    const DevPtr<speq_read_report> drep = DevPtr<speq_read_report>::alloc(most, who);
+    const DevPtr<uint64_t> dset = DevPtr<uint64_t>::alloc(most * W, who);
     const StagedPass pass = [&](const uint8_t* d_seq, const uint8_t* d_qual, const uint64_t* d_off, uint64_t r0,
                                 uint64_t n) {  // (the results leave with the batch's one stream wait)
         const uint64_t units = n / per, u0 = r0 / per;
-        report_device_impl(d, d_seq, d_qual, d_off, n, p, static_cast<speq_read_report*>(drep.p),
-                           static_cast<uint64_t*>(dset.p), d->stream);
-        HIP_OK(hipMemcpyAsync(reports + u0, drep.p, units * sizeof(speq_read_report), hipMemcpyDeviceToHost, d->stream));
-        HIP_OK(hipMemcpyAsync(sets + u0 * W, dset.p, units * W * 8, hipMemcpyDeviceToHost, d->stream));
+        report_device_impl(d, d_seq, d_qual, d_off, n, p, drep.get(), dset.get(), d->stream);
+        HIP_OK(hipMemcpyAsync(reports + u0, drep.get(), units * sizeof(speq_read_report), hipMemcpyDeviceToHost,
+                              d->stream));
+        HIP_OK(hipMemcpyAsync(sets + u0 * W, dset.get(), units * W * 8, hipMemcpyDeviceToHost, d->stream));
     };
     for_staged_batches(who, d, seq, qual, offsets, n_reads, per, pass);
 }

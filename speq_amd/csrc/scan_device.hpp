@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_mem.hpp"
 #include "scan_plan.hpp"
 #include "speq_errors.hpp"
 
@@ -411,13 +412,27 @@ inline void upload_bytes(void* dst, const void* src, size_t bytes) {
 }
 
 template <typename T>
-T* dev_upload(const std::vector<T>& v) {
-    if (v.empty()) return nullptr;
-    void* p = nullptr;
-    HIP_OK(hipMalloc(&p, v.size() * sizeof(T)));
-    upload_bytes(p, v.data(), v.size() * sizeof(T));
-    return static_cast<T*>(p);
+DevPtr<T> dev_upload(const std::vector<T>& v) {  // (empty: a null owner)
+    if (v.empty()) return {};
+    DevPtr<T> p = DevPtr<T>::alloc(v.size(), "dev_upload");
+    upload_bytes(p.get(), v.data(), v.size() * sizeof(T));
+    return p;
 }
+
+// Waits for `stream` when it goes. Declared after the buffers that work enqueued on the stream reads or writes, it is
+// destroyed before them: on every way out, an exception included, the work has ended before they are freed.
+// dismiss(): the buffers leave with the caller, whose own guard takes the wait over.
+struct SyncOnExit {
+    hipStream_t stream;
+    bool armed = true;
+    explicit SyncOnExit(hipStream_t s) : stream(s) {}
+    ~SyncOnExit() {
+        if (armed) (void)hipStreamSynchronize(stream);
+    }
+    void dismiss() { armed = false; }
+    SyncOnExit(const SyncOnExit&) = delete;
+    SyncOnExit& operator=(const SyncOnExit&) = delete;
+};
 
 struct DeviceGuard {
     int prev = -1;

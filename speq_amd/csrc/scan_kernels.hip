@@ -1226,8 +1226,8 @@ void build_sparse(speq_device_index* d) {
         if (Q % 96 == 0) rk[nbk - 1].count = cnt;
         d->present[lvl] = cnt;
         if (iv.empty()) iv.assign(2, 0u);
-        d->sparse_rank[lvl] = reinterpret_cast<const uint4*>(d->track(dev_upload(rk)));
-        d->sparse_iv[lvl] = reinterpret_cast<const uint2*>(d->track(dev_upload(iv)));
+        d->sparse_rank[lvl] = reinterpret_cast<const uint4*>(d->adopt(dev_upload(rk)));
+        d->sparse_iv[lvl] = reinterpret_cast<const uint2*>(d->adopt(dev_upload(iv)));
     }
     d->sparse_built = true;
 }
@@ -1293,121 +1293,89 @@ speq_device_index::KmerTable build_ktab(speq_device_index* d, uint32_t k) {
     }
     const uint64_t total = cum[d->n_texts];
     speq_device_index::KmerTable kt;
-    void* keys = nullptr;
-    uint64_t* d_cum = nullptr;
-    unsigned long long* d_cnt = nullptr;
-    void* tab = nullptr;       // compact-table build: freed here unless handed to the replica
-    uint2* multi = nullptr;
-    unsigned int* d_nm = nullptr;
-    auto cleanup = [&] {
-        (void)hipStreamSynchronize(d->stream);
-        if (keys) (void)hipFree(keys);
-        if (d_cum) (void)hipFree(d_cum);
-        if (d_cnt) (void)hipFree(d_cnt);
-        if (tab) (void)hipFree(tab);
-        if (multi) (void)hipFree(multi);
-        if (d_nm) (void)hipFree(d_nm);
-        keys = nullptr;
-        d_cum = nullptr;
-        d_cnt = nullptr;
-        tab = nullptr;
-        multi = nullptr;
-        d_nm = nullptr;
-    };
-    try {
-        unsigned long long distinct = 0;
-        const uint64_t slots = next_pow2(std::max<uint64_t>(2 * total, 64));
-        // too large for 32-bit bucket hashing, or for the free HBM (key set + a table of up to 4 slots per window):
-        // no table, scans of this k use LF steps (same results)
-        size_t free_b = 0, total_b = 0;
-        HIP_OK(hipMemGetInfo(&free_b, &total_b));
-        const uint64_t need = slots * 8 + next_pow2(std::max<uint64_t>(1, total * d->kt_slots / KT_BSLOTS)) * 16 * KT_BSLOTS;
-        if (slots > (1ull << 32) || need > free_b / 10 * 9) return kt;  // kt.table == nullptr
-        if (total > 0) {
-            HIP_OK(hipMalloc(&keys, slots * 8));
-            HIP_OK(hipMalloc(&d_cum, cum.size() * 8));
-            HIP_OK(hipMalloc(&d_cnt, 8));
-            HIP_OK(hipMemsetAsync(keys, 0xFF, slots * 8, d->stream));
-            HIP_OK(hipMemsetAsync(d_cnt, 0, 8, d->stream));
-            HIP_OK(hipMemcpyAsync(d_cum, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, d->stream));
-            const uint64_t runs = (total + KT_RUN - 1) / KT_RUN;
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((runs + 255) / 256, 8192);
-            hipLaunchKernelGGL(k_ktab_keys, dim3(grid), dim3(256), 0, d->stream, d->d_text, d->d_text_start, d_cum,
-                               d->n_texts, total, k, reinterpret_cast<unsigned long long*>(keys), slots - 1, d_cnt);
-            HIP_OK(hipGetLastError());
-            HIP_OK(hipMemcpyAsync(&distinct, d_cnt, 8, hipMemcpyDeviceToHost, d->stream));
-            HIP_OK(hipStreamSynchronize(d->stream));
-        }
-        kt.distinct = distinct;
-        // compact form first (k <= KT8_MAX_K): sized for the load factor kt_load8; if the multi-group k-mers outgrow the
-        // payload bits, fall through to the 16-B-slot form
-        const uint32_t pbits = 64u - 2u * k;
-        const uint64_t multi_cap = std::min<uint64_t>(distinct, (1ull << (pbits - 1u)) - 2u);
-        const uint64_t nb8 = std::max<uint64_t>(1, (uint64_t)((double)distinct * 100.0 / (8.0 * d->kt_load8)) + 1);
-        // the fill writes the multi-group k-mers into a scratch array of the worst-case size (every distinct k-mer),
-        // copied to one of the exact size afterwards; the free-memory check covers the scratch
-        const bool try_compact = d->kt_compact && KT_BSLOTS == 4 && k <= KT8_MAX_K && distinct > 0 && nb8 < (1ull << 32);
-        if (try_compact && nb8 * 64 + std::max<uint64_t>(multi_cap, 1) * 8 > free_b / 10 * 9) {
-            cleanup();
-            return kt;  // kt.table == nullptr: LF steps
-        }
-        if (try_compact) {
-            HIP_OK(hipMalloc(&tab, nb8 * 64));
-            HIP_OK(hipMalloc(&multi, std::max<uint64_t>(multi_cap, 1) * 8));
-            HIP_OK(hipMalloc(&d_nm, 4));
-            HIP_OK(hipMemsetAsync(tab, 0xFF, nb8 * 64, d->stream));
-            HIP_OK(hipMemsetAsync(d_nm, 0, 4, d->stream));
-            const DevView v = scan_view(d, k);
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((slots + 255) / 256, 16384);
-            hipLaunchKernelGGL(k_ktab_fill8, dim3(grid), dim3(256), 0, d->stream, v,
-                               reinterpret_cast<const unsigned long long*>(keys), slots, k,
-                               reinterpret_cast<unsigned long long*>(tab), (uint32_t)nb8, multi, d_nm,
-                               (uint32_t)multi_cap);
-            HIP_OK(hipGetLastError());
-            unsigned int n_multi = 0;
-            HIP_OK(hipMemcpyAsync(&n_multi, d_nm, 4, hipMemcpyDeviceToHost, d->stream));
-            HIP_OK(hipStreamSynchronize(d->stream));
-            if (n_multi <= multi_cap) {
-                uint2* exact = nullptr;
-                HIP_OK(hipMalloc(&exact, std::max<uint64_t>(n_multi, 1) * 8));
-                if (n_multi)
-                    HIP_OK(hipMemcpyAsync(exact, multi, (uint64_t)n_multi * 8, hipMemcpyDeviceToDevice, d->stream));
-                HIP_OK(hipStreamSynchronize(d->stream));
-                kt.compact = true;
-                kt.table = reinterpret_cast<uint4*>(d->track(tab));
-                kt.multi = d->track(exact);
-                kt.buckets = nb8;
-                kt.bytes = nb8 * 64 + std::max<uint64_t>(n_multi, 1) * 8;  // what the replica keeps
-                tab = nullptr;  // owned by the replica now
-                cleanup();
-                kt.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-                return kt;
-            }
-            (void)hipFree(tab);
-            (void)hipFree(multi);
-            (void)hipFree(d_nm);
-            tab = nullptr;
-            multi = nullptr;
-            d_nm = nullptr;
-        }
-        kt.buckets = next_pow2(std::max<uint64_t>(1, (distinct * d->kt_slots + KT_BSLOTS - 1) / KT_BSLOTS));
-        kt.bytes = kt.buckets * 16 * KT_BSLOTS;
-        HIP_OK(hipMalloc(&kt.table, kt.buckets * 16 * KT_BSLOTS));
-        d->track(kt.table);
-        HIP_OK(hipMemsetAsync(kt.table, 0xFF, kt.buckets * 16 * KT_BSLOTS, d->stream));
-        if (distinct > 0) {
-            const DevView v = scan_view(d, k);
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((slots + 255) / 256, 16384);
-            hipLaunchKernelGGL(k_ktab_fill, dim3(grid), dim3(256), 0, d->stream, v,
-                               reinterpret_cast<const unsigned long long*>(keys), slots, k, kt.table, kt.buckets - 1);
-            HIP_OK(hipGetLastError());
-        }
+    const char* who = "build_ktab";
+    DevPtr<unsigned long long> keys, d_cnt;
+    DevPtr<uint64_t> d_cum;
+    unsigned long long distinct = 0;
+    const uint64_t slots = next_pow2(std::max<uint64_t>(2 * total, 64));
+    // too large for 32-bit bucket hashing, or for the free HBM (key set + a table of up to 4 slots per window):
+    // no table, scans of this k use LF steps (same results)
+    size_t free_b = 0, total_b = 0;
+    HIP_OK(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t need = slots * 8 + next_pow2(std::max<uint64_t>(1, total * d->kt_slots / KT_BSLOTS)) * 16 * KT_BSLOTS;
+    if (slots > (1ull << 32) || need > free_b / 10 * 9) return kt;  // kt.table == nullptr
+    SyncOnExit sync(d->stream);  // after the buffers above, and every later one lives in a scope inside its own
+    if (total > 0) {
+        keys = DevPtr<unsigned long long>::alloc(slots, who);
+        d_cum = DevPtr<uint64_t>::alloc(cum.size(), who);
+        d_cnt = DevPtr<unsigned long long>::alloc(1, who);
+        HIP_OK(hipMemsetAsync(keys.get(), 0xFF, slots * 8, d->stream));
+        HIP_OK(hipMemsetAsync(d_cnt.get(), 0, 8, d->stream));
+        HIP_OK(hipMemcpyAsync(d_cum.get(), cum.data(), cum.size() * 8, hipMemcpyHostToDevice, d->stream));
+        const uint64_t runs = (total + KT_RUN - 1) / KT_RUN;
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((runs + 255) / 256, 8192);
+        hipLaunchKernelGGL(k_ktab_keys, dim3(grid), dim3(256), 0, d->stream, d->d_text, d->d_text_start, d_cum.get(),
+                           d->n_texts, total, k, keys.get(), slots - 1, d_cnt.get());
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(&distinct, d_cnt.get(), 8, hipMemcpyDeviceToHost, d->stream));
         HIP_OK(hipStreamSynchronize(d->stream));
-    } catch (...) {
-        cleanup();
-        throw;
     }
-    cleanup();
+    kt.distinct = distinct;
+    // compact form first (k <= KT8_MAX_K): sized for the load factor kt_load8; if the multi-group k-mers outgrow the
+    // payload bits, fall through to the 16-B-slot form
+    const uint32_t pbits = 64u - 2u * k;
+    const uint64_t multi_cap = std::min<uint64_t>(distinct, (1ull << (pbits - 1u)) - 2u);
+    const uint64_t nb8 = std::max<uint64_t>(1, (uint64_t)((double)distinct * 100.0 / (8.0 * d->kt_load8)) + 1);
+    // the fill writes the multi-group k-mers into a scratch array of the worst-case size (every distinct k-mer),
+    // copied to one of the exact size afterwards; the free-memory check covers the scratch
+    const bool try_compact = d->kt_compact && KT_BSLOTS == 4 && k <= KT8_MAX_K && distinct > 0 && nb8 < (1ull << 32);
+    if (try_compact && nb8 * 64 + std::max<uint64_t>(multi_cap, 1) * 8 > free_b / 10 * 9)
+        return kt;  // kt.table == nullptr: LF steps
+    if (try_compact) {
+        DevPtr<unsigned long long> tab = DevPtr<unsigned long long>::alloc(nb8 * 8, who);
+        DevPtr<uint2> multi = DevPtr<uint2>::alloc(std::max<uint64_t>(multi_cap, 1), who);
+        DevPtr<unsigned int> d_nm = DevPtr<unsigned int>::alloc(1, who);
+        SyncOnExit sync_fill(d->stream);
+        HIP_OK(hipMemsetAsync(tab.get(), 0xFF, nb8 * 64, d->stream));
+        HIP_OK(hipMemsetAsync(d_nm.get(), 0, 4, d->stream));
+        const DevView v = scan_view(d, k);
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((slots + 255) / 256, 16384);
+        hipLaunchKernelGGL(k_ktab_fill8, dim3(grid), dim3(256), 0, d->stream, v, keys.get(), slots, k, tab.get(),
+                           (uint32_t)nb8, multi.get(), d_nm.get(), (uint32_t)multi_cap);
+        HIP_OK(hipGetLastError());
+        unsigned int n_multi = 0;
+        HIP_OK(hipMemcpyAsync(&n_multi, d_nm.get(), 4, hipMemcpyDeviceToHost, d->stream));
+        HIP_OK(hipStreamSynchronize(d->stream));
+        if (n_multi <= multi_cap) {
+            DevPtr<uint2> exact = DevPtr<uint2>::alloc(std::max<uint64_t>(n_multi, 1), who);
+            SyncOnExit sync_copy(d->stream);
+            if (n_multi)
+                HIP_OK(hipMemcpyAsync(exact.get(), multi.get(), (uint64_t)n_multi * 8, hipMemcpyDeviceToDevice,
+                                      d->stream));
+            HIP_OK(hipStreamSynchronize(d->stream));
+            kt.compact = true;  // complete: the replica takes the table and the exact array
+            kt.table = reinterpret_cast<uint4*>(d->adopt(std::move(tab)));
+            kt.multi = d->adopt(std::move(exact));
+            kt.buckets = nb8;
+            kt.bytes = nb8 * 64 + std::max<uint64_t>(n_multi, 1) * 8;  // what the replica keeps
+            kt.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            return kt;
+        }
+    }
+    kt.buckets = next_pow2(std::max<uint64_t>(1, (distinct * d->kt_slots + KT_BSLOTS - 1) / KT_BSLOTS));
+    kt.bytes = kt.buckets * 16 * KT_BSLOTS;
+    DevPtr<uint4> wide = DevPtr<uint4>::alloc(kt.buckets * KT_BSLOTS, who);
+    SyncOnExit sync_wide(d->stream);
+    HIP_OK(hipMemsetAsync(wide.get(), 0xFF, kt.buckets * 16 * KT_BSLOTS, d->stream));
+    if (distinct > 0) {
+        const DevView v = scan_view(d, k);
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((slots + 255) / 256, 16384);
+        hipLaunchKernelGGL(k_ktab_fill, dim3(grid), dim3(256), 0, d->stream, v, keys.get(), slots, k, wide.get(),
+                           kt.buckets - 1);
+        HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipStreamSynchronize(d->stream));
+    kt.table = d->adopt(std::move(wide));  // filled: the replica takes it
     kt.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return kt;
 }
@@ -1638,17 +1606,17 @@ int speq_device_open(const speq_index* idx, int device, speq_device_index** out)
         d->n_texts = fm.n_texts;
         d->text_start = fm.text_start;
         DevView& v = d->view;
-        v.occ = reinterpret_cast<const uint4*>(d->track(dev_upload(fm.occ)));
+        v.occ = reinterpret_cast<const uint4*>(d->adopt(dev_upload(fm.occ)));
         v.nb = (uint32_t)fm.n_blocks();
-        v.occ2 = reinterpret_cast<const uint4*>(d->track(dev_upload(fm.occ2)));
-        v.occ3 = reinterpret_cast<const uint4*>(d->track(dev_upload(fm.occ3)));
-        v.runs = reinterpret_cast<const uint4*>(d->track(dev_upload(fm.runs)));
-        v.run_label = d->track(dev_upload(fm.run_label));
-        v.lab = d->track(dev_upload(fm.lab));
-        v.prefix = reinterpret_cast<const uint2*>(d->track(dev_upload(fm.prefix)));
+        v.occ2 = reinterpret_cast<const uint4*>(d->adopt(dev_upload(fm.occ2)));
+        v.occ3 = reinterpret_cast<const uint4*>(d->adopt(dev_upload(fm.occ3)));
+        v.runs = reinterpret_cast<const uint4*>(d->adopt(dev_upload(fm.runs)));
+        v.run_label = d->adopt(dev_upload(fm.run_label));
+        v.lab = d->adopt(dev_upload(fm.lab));
+        v.prefix = reinterpret_cast<const uint2*>(d->adopt(dev_upload(fm.prefix)));
         d->prefix_level[0] = v.prefix;
-        d->prefix_level[1] = reinterpret_cast<const uint2*>(d->track(dev_upload(fm.prefix1)));
-        d->prefix_level[2] = reinterpret_cast<const uint2*>(d->track(dev_upload(fm.prefix2)));
+        d->prefix_level[1] = reinterpret_cast<const uint2*>(d->adopt(dev_upload(fm.prefix1)));
+        d->prefix_level[2] = reinterpret_cast<const uint2*>(d->adopt(dev_upload(fm.prefix2)));
         for (int lvl = 0; lvl < 3; ++lvl)  // (the sparse forms are built on first use: build_sparse)
             d->prefix_words[lvl] = (lvl == 0 ? fm.prefix : lvl == 1 ? fm.prefix1 : fm.prefix2).size();
         speq::startup_trace("device open: FM arrays");
@@ -1656,15 +1624,15 @@ int speq_device_open(const speq_index* idx, int device, speq_device_index** out)
         v.q = fm.prefix_q;
         d->base_q = fm.prefix_q;
         v.G = fm.n_groups;
-        d->d_text = d->track(dev_upload(fm.text));
-        d->d_text_start = d->track(dev_upload(fm.text_start));
-        d->d_text_group = d->track(dev_upload(fm.text_group));
+        d->d_text = d->adopt(dev_upload(fm.text));
+        d->d_text_start = d->adopt(dev_upload(fm.text_start));
+        d->d_text_group = d->adopt(dev_upload(fm.text_group));
         std::vector<double> lut(2 * QLUT_LEN);  // {1 - 1/10^(q/10) (fm_scanner.cpp:454), its reciprocal}
         for (uint32_t q = 0; q < QLUT_LEN; ++q) {
             lut[2 * q] = 1.0 - 1.0 / std::pow(10.0, (double)q / 10.0);
             lut[2 * q + 1] = 1.0 / lut[2 * q];  // q = 0: inf, never used (a passing window has every q > cutoff >= 0)
         }
-        d->d_qlut = d->track(dev_upload(lut));
+        d->d_qlut = d->adopt(dev_upload(lut));
         speq::startup_trace("device open: uploads");
         d->stream = static_cast<hipStream_t>(speq::pooled_stream(device));
         hipDeviceProp_t prop;
@@ -1701,7 +1669,7 @@ speq_device_index::~speq_device_index() {
         (void)hipEventDestroy(e.first);
         (void)hipEventDestroy(e.second);
     }
-    for (void* p : allocs) (void)hipFree(p);
+    allocs.clear();  // here, while the replica's device is current (members go after the body)
     if (stream) (void)hipStreamDestroy(stream);
     if (switched) (void)hipSetDevice(prev);
 }
@@ -1737,14 +1705,10 @@ int speq_scan_reads_device_stats(speq_device_index* d, const uint8_t* d_seq, con
         DeviceGuard g(d->device);
         // the counters' buffer travels with this launch only (UnitSrc::ax_stats), so ordinary scans of the same
         // replica from other threads never run the instrumented kernel
-        unsigned long long* ds = nullptr;
-        HIP_OK(hipMalloc(&ds, SPEQ_AX_STATS_N * 8));
-        struct Release {
-            unsigned long long*& p;
-            ~Release() {
-                if (p) (void)hipFree(p);
-            }
-        } release{ds};
+        const DevPtr<unsigned long long> stats_buf =
+            DevPtr<unsigned long long>::alloc(SPEQ_AX_STATS_N, "speq_scan_reads_device_stats");
+        SyncOnExit sync(d->stream);
+        unsigned long long* ds = stats_buf.get();
         HIP_OK(hipMemsetAsync(ds, 0, SPEQ_AX_STATS_N * 8, d->stream));
         HIP_OK(hipStreamSynchronize(d->stream));
         const int kernel =
@@ -1772,12 +1736,12 @@ int speq_em_create(const speq_index* idx, speq_device_index* d, speq_em** out) {
         em->dev = d;
         em->n = idx->fm.n;
         em->G = idx->fm.n_groups;
-        HIP_OK(hipMalloc(&em->d_mult, em->n * 4));
-        HIP_OK(hipMalloc(&em->d_hi, em->n * 4));
-        HIP_OK(hipMemset(em->d_mult, 0, em->n * 4));
+        em->d_mult = DevPtr<uint32_t>::alloc(em->n, "speq_em_create");
+        em->d_hi = DevPtr<uint32_t>::alloc(em->n, "speq_em_create");
+        HIP_OK(hipMemset(em->d_mult.get(), 0, em->n * 4));
         // interval ends are merged across ranks / replicas with a max (speq_em_allreduce, k_em_merge): a position this
         // replica never wrote must hold 0, not whatever the allocation held
-        HIP_OK(hipMemset(em->d_hi, 0, em->n * 4));
+        HIP_OK(hipMemset(em->d_hi.get(), 0, em->n * 4));
         *out = em.release();
     });
 }
@@ -1795,8 +1759,8 @@ int speq_em_scan_reads_device(speq_em* em, const uint8_t* d_seq, const uint8_t* 
                               void* stream) {
     return speq::guarded([&] {
         if (!em || em->finalized) throw std::invalid_argument("speq_em_scan_reads_device: bad or finalized histogram");
-        scan_device_impl(em->dev, d_seq, d_qual, d_offsets, n_reads, p, d_counts, d_weights, em->d_mult, em->d_hi,
-                         static_cast<hipStream_t>(stream));
+        scan_device_impl(em->dev, d_seq, d_qual, d_offsets, n_reads, p, d_counts, d_weights, em->d_mult.get(),
+                         em->d_hi.get(), static_cast<hipStream_t>(stream));
     });
 }
 
@@ -1812,13 +1776,15 @@ int speq_em_finalize(speq_em* em, uint32_t threads) {
         const uint64_t n = em->n;
         const uint32_t nb = (uint32_t)((n + EM_TILE - 1) / EM_TILE);
         hipStream_t st = em->dev->stream;
-        uint32_t* d_cnt = nullptr;
-        uint32_t* d_out = nullptr;
-        HIP_OK(hipMalloc(&d_cnt, ((uint64_t)nb + 1) * 4));
+        const char* who = "speq_em_finalize";
         uint32_t nnz = 0;
-        try {
+        std::unique_ptr<uint32_t[]> tri;
+        {
+            DevPtr<uint32_t> cnt_buf = DevPtr<uint32_t>::alloc((uint64_t)nb + 1, who), out_buf;
+            SyncOnExit sync(st);
+            uint32_t* d_cnt = cnt_buf.get();
             if (nb) {
-                hipLaunchKernelGGL(k_em_count, dim3(nb), dim3(256), 0, st, em->d_mult, n, d_cnt);
+                hipLaunchKernelGGL(k_em_count, dim3(nb), dim3(256), 0, st, em->d_mult.get(), n, d_cnt);
                 HIP_OK(hipGetLastError());
             }
             hipLaunchKernelGGL(k_em_scan, dim3(1), dim3(1024), 0, st, d_cnt, nb);
@@ -1827,11 +1793,12 @@ int speq_em_finalize(speq_em* em, uint32_t threads) {
             HIP_OK(hipStreamSynchronize(st));
             // (lo, mult, hi) in one allocation, copied back by DMA into host memory page-locked for the copy (a
             // pageable copy of the three arrays took 8-9 ms at config 3)
-            std::unique_ptr<uint32_t[]> tri(new uint32_t[3ull * std::max<uint32_t>(nnz, 1)]);
+            tri.reset(new uint32_t[3ull * std::max<uint32_t>(nnz, 1)]);
             if (nnz) {
-                HIP_OK(hipMalloc(&d_out, (uint64_t)nnz * 12));
-                hipLaunchKernelGGL(k_em_compact, dim3(nb), dim3(256), 0, st, em->d_mult, em->d_hi, n, d_cnt, d_out,
-                                   d_out + nnz, d_out + 2ull * nnz);
+                out_buf = DevPtr<uint32_t>::alloc(3ull * nnz, who);
+                uint32_t* d_out = out_buf.get();
+                hipLaunchKernelGGL(k_em_compact, dim3(nb), dim3(256), 0, st, em->d_mult.get(), em->d_hi.get(), n, d_cnt,
+                                   d_out, d_out + nnz, d_out + 2ull * nnz);
                 HIP_OK(hipGetLastError());
                 // (the compaction first, then a synchronous copy: an asynchronous device-to-host copy on the
                 // replica's stream paid about 8 ms of first-use cost in a `speq scan` process, this one 0.1 ms)
@@ -1842,19 +1809,10 @@ int speq_em_finalize(speq_em* em, uint32_t threads) {
                 if (reg) (void)hipHostUnregister(tri.get());
                 HIP_OK(ce);
             }
-            (void)hipFree(d_cnt);
-            if (d_out) (void)hipFree(d_out);
-            d_cnt = d_out = nullptr;
-            speq::em_build_rows(*em, tri.get(), tri.get() + nnz, tri.get() + 2ull * nnz, nnz);
-        } catch (...) {
-            (void)hipStreamSynchronize(st);
-            if (d_cnt) (void)hipFree(d_cnt);
-            if (d_out) (void)hipFree(d_out);
-            throw;
-        }
-        (void)hipFree(em->d_mult);
-        (void)hipFree(em->d_hi);
-        em->d_mult = em->d_hi = nullptr;
+        }  // (the two buffers go before the rows are built)
+        speq::em_build_rows(*em, tri.get(), tri.get() + nnz, tri.get() + 2ull * nnz, nnz);
+        em->d_mult.reset();
+        em->d_hi.reset();
     });
 }
 
@@ -1873,43 +1831,41 @@ int speq_em_merge(speq_em* dst, speq_em* src) {
         }
         DeviceGuard g(dst->dev->device);
         HIP_OK(hipDeviceSynchronize());
-        uint32_t *m = src->d_mult, *h = src->d_hi, *tmp = nullptr;
+        uint32_t *m = src->d_mult.get(), *h = src->d_hi.get();
+        DevPtr<uint32_t> tmp;
+        SyncOnExit sync(dst->dev->stream);
         if (src->dev->device != dst->dev->device) {
-            HIP_OK(hipMalloc(&tmp, dst->n * 8));
-            m = tmp;
-            h = tmp + dst->n;
-            HIP_OK(hipMemcpyPeerAsync(m, dst->dev->device, src->d_mult, src->dev->device, dst->n * 4, dst->dev->stream));
-            HIP_OK(hipMemcpyPeerAsync(h, dst->dev->device, src->d_hi, src->dev->device, dst->n * 4, dst->dev->stream));
+            tmp = DevPtr<uint32_t>::alloc(dst->n * 2, "speq_em_merge");
+            m = tmp.get();
+            h = tmp.get() + dst->n;
+            HIP_OK(hipMemcpyPeerAsync(m, dst->dev->device, src->d_mult.get(), src->dev->device, dst->n * 4,
+                                      dst->dev->stream));
+            HIP_OK(hipMemcpyPeerAsync(h, dst->dev->device, src->d_hi.get(), src->dev->device, dst->n * 4,
+                                      dst->dev->stream));
         }
         const uint64_t blocks = std::min<uint64_t>((dst->n + 1023) / 1024, 65536);
         hipLaunchKernelGGL(k_em_merge, dim3((uint32_t)std::max<uint64_t>(blocks, 1)), dim3(256), 0, dst->dev->stream,
-                           dst->d_mult, dst->d_hi, m, h, dst->n);
+                           dst->d_mult.get(), dst->d_hi.get(), m, h, dst->n);
         HIP_OK(hipGetLastError());
         HIP_OK(hipStreamSynchronize(dst->dev->stream));
-        if (tmp) HIP_OK(hipFree(tmp));
-        {
-            DeviceGuard gs(src->dev->device);
-            (void)hipFree(src->d_mult);
-            (void)hipFree(src->d_hi);
-        }
-        src->d_mult = src->d_hi = nullptr;
+        tmp.reset();
+        DeviceGuard gs(src->dev->device);
+        src->d_mult.reset();
+        src->d_hi.reset();
     });
 }
 
 void speq_em_free(speq_em* em) {
-    if (!em) return;
-    if (em->d_mult) (void)hipFree(em->d_mult);
-    if (em->d_hi) (void)hipFree(em->d_hi);
-    delete em;
+    delete em;  // (null: nothing; the histogram owns its two arrays)
 }
 
 }  // extern "C"
 
 namespace {
 // Enqueues the .dat pass over shard `shard` of `n_shards` equal slices of the flattened reference windows (every
-// text's fwd and rc windows in text order); the returned device buffer of window prefix sums must stay alive until
-// the launch completes (freed by the caller after synchronizing `st`).
-uint64_t* launch_ref_shard(speq_device_index* d, uint32_t k, uint32_t shard, uint32_t n_shards, uint64_t* d_u_ref,
+// text's fwd and rc windows in text order); the returned owner of the window prefix sums (null: an empty shard) must
+// stay alive until the launch completes: the caller synchronises `st` before it goes.
+DevPtr<uint64_t> launch_ref_shard(speq_device_index* d, uint32_t k, uint32_t shard, uint32_t n_shards, uint64_t* d_u_ref,
                            uint64_t* d_tot_ref, hipStream_t st) {
     std::vector<uint64_t> cum(d->n_texts + 1, 0);
     for (uint32_t t = 0; t < d->n_texts; ++t) {
@@ -1918,14 +1874,14 @@ uint64_t* launch_ref_shard(speq_device_index* d, uint32_t k, uint32_t shard, uin
     }
     const uint64_t all = cum[d->n_texts];
     const uint64_t w0 = all * shard / n_shards, w1 = all * (shard + 1) / n_shards;
-    if (w1 == w0) return nullptr;
-    uint64_t* d_cum = nullptr;
-    HIP_OK(hipMalloc(&d_cum, cum.size() * 8));
-    HIP_OK(hipMemcpyAsync(d_cum, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, st));
+    if (w1 == w0) return {};
+    DevPtr<uint64_t> d_cum = DevPtr<uint64_t>::alloc(cum.size(), "launch_ref_shard");
+    SyncOnExit sync(st);  // (a throw below: the copy has ended before d_cum goes)
+    HIP_OK(hipMemcpyAsync(d_cum.get(), cum.data(), cum.size() * 8, hipMemcpyHostToDevice, st));
     UnitSrc src{};
     src.seq = d->d_text;
     src.off = d->d_text_start;
-    src.cum_win = d_cum;
+    src.cum_win = d_cum.get();
     src.unit_group = d->d_text_group;
     src.n_units = d->n_texts;
     src.total_windows = w1 - w0;
@@ -1934,6 +1890,7 @@ uint64_t* launch_ref_shard(speq_device_index* d, uint32_t k, uint32_t shard, uin
     src.k = k;
     launch_scan(d, KM_REF, false, src, st, reinterpret_cast<unsigned long long*>(d_u_ref),
                 reinterpret_cast<unsigned long long*>(d_tot_ref), nullptr);
+    sync.dismiss();
     return d_cum;
 }
 }  // namespace
@@ -1946,10 +1903,8 @@ int speq_ref_unique_device(speq_device_index* d, uint32_t k, uint64_t* d_u_ref, 
         if (k < 1 || k > MAX_K) throw std::invalid_argument("speq_ref_unique_device: k must be in [1, 4096]");
         DeviceGuard g(d->device);
         hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = the null (default) stream
-        uint64_t* d_cum = launch_ref_shard(d, k, 0, 1, d_u_ref, d_tot_ref, st);
-        if (!d_cum) return;
-        HIP_OK(hipStreamSynchronize(st));  // d_cum is freed below
-        HIP_OK(hipFree(d_cum));
+        const DevPtr<uint64_t> d_cum = launch_ref_shard(d, k, 0, 1, d_u_ref, d_tot_ref, st);
+        if (d_cum) HIP_OK(hipStreamSynchronize(st));  // before d_cum goes
     });
 }
 
@@ -1965,40 +1920,39 @@ int speq_ref_unique_multi(speq_device_index* const* ds, uint32_t n_devices, uint
             if (!ds[i] || ds[i]->G != ds[0]->G || ds[i]->view.n != ds[0]->view.n)
                 throw std::invalid_argument("speq_ref_unique_multi: replicas of different indexes");
         const uint32_t G = ds[0]->G;
-        struct Shard {
-            uint64_t* buf = nullptr;
-            uint64_t* cum = nullptr;
+        struct Shard {  // its device buffers go once their stream has been waited for, with their device current
+            speq_device_index* d = nullptr;
+            DevPtr<uint64_t> buf, cum;
             std::vector<uint64_t> host;
+            void release() {  // (from the destructor too: nothing here throws)
+                if (!buf && !cum) return;
+                int prev = -1;
+                (void)hipGetDevice(&prev);
+                (void)hipSetDevice(d->device);
+                (void)hipStreamSynchronize(d->stream);
+                buf.reset();
+                cum.reset();
+                if (prev >= 0) (void)hipSetDevice(prev);
+            }
+            Shard() = default;
+            ~Shard() { release(); }
         };
         std::vector<Shard> sh(n_devices);
-        auto release = [&] {
-            for (uint32_t i = 0; i < n_devices; ++i) {
-                DeviceGuard g(ds[i]->device);
-                if (sh[i].buf || sh[i].cum) (void)hipStreamSynchronize(ds[i]->stream);
-                if (sh[i].buf) (void)hipFree(sh[i].buf);
-                if (sh[i].cum) (void)hipFree(sh[i].cum);
-                sh[i].buf = sh[i].cum = nullptr;
-            }
-        };
-        try {
-            for (uint32_t i = 0; i < n_devices; ++i) {
-                speq_device_index* d = ds[i];
-                DeviceGuard g(d->device);
-                HIP_OK(hipMalloc(&sh[i].buf, 2ull * G * 8));
-                HIP_OK(hipMemsetAsync(sh[i].buf, 0, 2ull * G * 8, d->stream));
-                sh[i].cum = launch_ref_shard(d, k, i, n_devices, sh[i].buf, sh[i].buf + G, d->stream);
-                sh[i].host.assign(2ull * G, 0);
-                HIP_OK(hipMemcpyAsync(sh[i].host.data(), sh[i].buf, 2ull * G * 8, hipMemcpyDeviceToHost, d->stream));
-            }
-            for (uint32_t i = 0; i < n_devices; ++i) {
-                DeviceGuard g(ds[i]->device);
-                HIP_OK(hipStreamSynchronize(ds[i]->stream));
-            }
-        } catch (...) {
-            release();
-            throw;
+        for (uint32_t i = 0; i < n_devices; ++i) {
+            speq_device_index* d = sh[i].d = ds[i];
+            DeviceGuard g(d->device);
+            sh[i].buf = DevPtr<uint64_t>::alloc(2ull * G, "speq_ref_unique_multi");
+            uint64_t* buf = sh[i].buf.get();
+            HIP_OK(hipMemsetAsync(buf, 0, 2ull * G * 8, d->stream));
+            sh[i].cum = launch_ref_shard(d, k, i, n_devices, buf, buf + G, d->stream);
+            sh[i].host.assign(2ull * G, 0);
+            HIP_OK(hipMemcpyAsync(sh[i].host.data(), buf, 2ull * G * 8, hipMemcpyDeviceToHost, d->stream));
         }
-        release();
+        for (uint32_t i = 0; i < n_devices; ++i) {
+            DeviceGuard g(ds[i]->device);
+            HIP_OK(hipStreamSynchronize(ds[i]->stream));
+        }
+        for (Shard& s : sh) s.release();
         std::fill(u_ref, u_ref + G, 0);
         std::fill(tot_ref, tot_ref + G, 0);
         for (const Shard& s : sh)
@@ -2014,19 +1968,14 @@ int speq_ref_unique(speq_device_index* d, uint32_t k, uint64_t* u_ref, uint64_t*
         if (!d || !u_ref || !tot_ref) throw std::invalid_argument("speq_ref_unique: null argument");
         DeviceGuard g(d->device);
         const uint32_t G = d->G;
-        uint64_t* buf = nullptr;
-        HIP_OK(hipMalloc(&buf, 2ull * G * 8));
+        const DevPtr<uint64_t> owner = DevPtr<uint64_t>::alloc(2ull * G, "speq_ref_unique");
+        SyncOnExit sync(d->stream);
+        uint64_t* buf = owner.get();
         HIP_OK(hipMemsetAsync(buf, 0, 2ull * G * 8, d->stream));
-        int rc = speq_ref_unique_device(d, k, buf, buf + G, d->stream);
-        if (rc != SPEQ_OK) {
-            std::string msg = speq_last_error();
-            (void)hipFree(buf);
-            throw speq::DeviceError(msg);
-        }
+        if (speq_ref_unique_device(d, k, buf, buf + G, d->stream) != SPEQ_OK) throw speq::DeviceError(speq_last_error());
         HIP_OK(hipMemcpyAsync(u_ref, buf, G * 8, hipMemcpyDeviceToHost, d->stream));
         HIP_OK(hipMemcpyAsync(tot_ref, buf + G, G * 8, hipMemcpyDeviceToHost, d->stream));
         HIP_OK(hipStreamSynchronize(d->stream));
-        HIP_OK(hipFree(buf));
     });
 }
 
@@ -2038,23 +1987,14 @@ int speq_ref_unique_shard(speq_device_index* d, uint32_t k, uint32_t shard, uint
         if (n_shards == 0 || shard >= n_shards) throw std::invalid_argument("speq_ref_unique_shard: bad shard");
         DeviceGuard g(d->device);
         const uint32_t G = d->G;
-        uint64_t* buf = nullptr;
-        uint64_t* d_cum = nullptr;
-        try {
-            HIP_OK(hipMalloc(&buf, 2ull * G * 8));
-            HIP_OK(hipMemsetAsync(buf, 0, 2ull * G * 8, d->stream));
-            d_cum = launch_ref_shard(d, k, shard, n_shards, buf, buf + G, d->stream);
-            HIP_OK(hipMemcpyAsync(u_ref, buf, G * 8, hipMemcpyDeviceToHost, d->stream));
-            HIP_OK(hipMemcpyAsync(tot_ref, buf + G, G * 8, hipMemcpyDeviceToHost, d->stream));
-            HIP_OK(hipStreamSynchronize(d->stream));
-        } catch (...) {
-            (void)hipStreamSynchronize(d->stream);
-            if (d_cum) (void)hipFree(d_cum);
-            if (buf) (void)hipFree(buf);
-            throw;
-        }
-        if (d_cum) HIP_OK(hipFree(d_cum));
-        HIP_OK(hipFree(buf));
+        DevPtr<uint64_t> owner = DevPtr<uint64_t>::alloc(2ull * G, "speq_ref_unique_shard"), d_cum;
+        SyncOnExit sync(d->stream);
+        uint64_t* buf = owner.get();
+        HIP_OK(hipMemsetAsync(buf, 0, 2ull * G * 8, d->stream));
+        d_cum = launch_ref_shard(d, k, shard, n_shards, buf, buf + G, d->stream);
+        HIP_OK(hipMemcpyAsync(u_ref, buf, G * 8, hipMemcpyDeviceToHost, d->stream));
+        HIP_OK(hipMemcpyAsync(tot_ref, buf + G, G * 8, hipMemcpyDeviceToHost, d->stream));
+        HIP_OK(hipStreamSynchronize(d->stream));
     });
 }
 
@@ -2243,8 +2183,8 @@ void em_clear(speq_em* em) {
     if (!em) return;
     if (em->finalized) throw std::logic_error("speq: EM histogram already finalized");
     DeviceGuard g(em->dev->device);
-    HIP_OK(hipMemset(em->d_mult, 0, em->n * 4));
-    HIP_OK(hipMemset(em->d_hi, 0, em->n * 4));
+    HIP_OK(hipMemset(em->d_mult.get(), 0, em->n * 4));
+    HIP_OK(hipMemset(em->d_hi.get(), 0, em->n * 4));
 }
 }  // namespace speq
 

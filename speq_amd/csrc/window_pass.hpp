@@ -75,28 +75,6 @@ __device__ __forceinline__ int search_tile(const DevView& I, const Rsrc& R, unsi
         bad = s == 4u || (uint32_t)q <= (cutoff);                        \
     }
 
-// a device allocation that does not fit: SPEQ_E_DEVICE through guarded(), SPEQ_E_NOMEM where the entry point says so
-struct OutOfDeviceMemory : speq::DeviceError {
-    using speq::DeviceError::DeviceError;
-};
-
-inline void dev_alloc(void** p, size_t bytes, const char* who) {
-    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        throw OutOfDeviceMemory(std::string(who) + ": out of device memory (" + std::to_string(bytes) + " bytes)");
-    }
-    if (e != hipSuccess) throw speq::DeviceError(std::string(who) + ": hipMalloc: " + hipGetErrorString(e));
-}
-
-struct DevBuf {
-    void* p = nullptr;
-    DevBuf(size_t bytes, const char* who) { dev_alloc(&p, bytes, who); }
-    ~DevBuf() { (void)hipFree(p); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-};
-
 // Host reads (checked: speq::check_host_reads) through a pass in batches of whole units: at most BATCH_RECORDS records
 // and (a single longer unit aside) BATCH_BYTES bases each. Bases, qualities and the offsets rebased to 0 are staged in
 // device buffers, pass(d_seq, d_qual, d_offsets, r0, n) issues its work for the n records from r0 on d->stream, and
@@ -114,14 +92,15 @@ inline void for_staged_batches(const char* who, speq_device_index* d, const uint
         const uint64_t n = r1 - r0, bytes = offsets[r1] - offsets[r0];
         rel.resize(n + 1);
         for (uint64_t i = 0; i <= n; ++i) rel[i] = offsets[r0 + i] - offsets[r0];
-        DevBuf ds(bytes, who), dq(bytes, who), dof((n + 1) * 8, who);
+        const DevPtr<uint8_t> ds = DevPtr<uint8_t>::alloc(bytes, who), dq = DevPtr<uint8_t>::alloc(bytes, who);
+        const DevPtr<uint64_t> dof = DevPtr<uint64_t>::alloc(n + 1, who);
+        SyncOnExit sync(d->stream);
         if (bytes) {
-            HIP_OK(hipMemcpyAsync(ds.p, seq + offsets[r0], bytes, hipMemcpyHostToDevice, d->stream));
-            HIP_OK(hipMemcpyAsync(dq.p, qual + offsets[r0], bytes, hipMemcpyHostToDevice, d->stream));
+            HIP_OK(hipMemcpyAsync(ds.get(), seq + offsets[r0], bytes, hipMemcpyHostToDevice, d->stream));
+            HIP_OK(hipMemcpyAsync(dq.get(), qual + offsets[r0], bytes, hipMemcpyHostToDevice, d->stream));
         }
-        HIP_OK(hipMemcpyAsync(dof.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, d->stream));
-        pass(static_cast<const uint8_t*>(ds.p), static_cast<const uint8_t*>(dq.p), static_cast<const uint64_t*>(dof.p),
-             r0, n);
+        HIP_OK(hipMemcpyAsync(dof.get(), rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, d->stream));
+        pass(ds.get(), dq.get(), dof.get(), r0, n);
         HIP_OK(hipStreamSynchronize(d->stream));
         r0 = r1;
     }
