@@ -17,7 +17,7 @@ OBJDIR   := build/obj
 
 LIB_HIP  := speq_amd/csrc/scan_kernels.hip speq_amd/csrc/ax_scan.hip speq_amd/csrc/build_gpu.hip speq_amd/csrc/fastq_gpu.hip \
             speq_amd/csrc/read_report.hip speq_amd/csrc/read_markers.hip speq_amd/csrc/read_bootstrap.hip \
-            speq_amd/csrc/read_dedup.hip
+            speq_amd/csrc/read_dedup.hip speq_amd/csrc/marker_track.hip
 LIB_CPP  := speq_amd/csrc/sais.cpp speq_amd/csrc/fm_index.cpp speq_amd/csrc/capi.cpp speq_amd/csrc/comm.cpp \
             speq_amd/csrc/host_io.cpp speq_amd/csrc/em.cpp speq_amd/csrc/pipeline.cpp \
             speq_amd/csrc/fastq_stream.cpp speq_amd/csrc/dev_mem.cpp

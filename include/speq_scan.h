@@ -210,7 +210,16 @@ int speq_report_reads(speq_device_index* d, const uint8_t* seq, const uint8_t* q
  * near 1 - exp(-hits / markers), while copies of a few k-mers (an amplicon, duplicates, a contaminating fragment)
  * give the same hits at a breadth near 0. Every passing window is searched exactly (no per-k structure), as in the
  * per-unit report: an opt-in pass, not the hot path. The handle holds 4 bytes per SA position on the replica's GPU;
- * the replica must outlive it. A marker's depth must stay below 2^31. The reference keeps none of this. */
+ * the replica must outlive it. A marker's depth must stay below 2^31. The reference keeps none of this.
+ *
+ * The marker track says where along each record the covered markers lie. A locus (r, p) is a window
+ * start p of fwd_r (text 2r), 0 <= p < nwin_r = max(L_r - k + 1, 0); it is a marker locus when its k-mer x is a marker
+ * (then of the record's own group). Its depth folds the strands: depth(x) + depth(rc(x)), or depth(x) alone when x is
+ * its own reverse complement (one k-mer, one marker, counted once). The depth belongs to the k-mer: a marker that lies
+ * at several loci (a repeat inside a record, identical records of one group) gives each of them its full depth, so the
+ * track's hits summed over a group are >= the group's hits above, and equal when every marker has one locus. Record r
+ * has ceil(nwin_r / bin) bins, bin b covering the loci [b * bin, min((b + 1) * bin, nwin_r)); a record shorter than k
+ * has none. Per bin: its marker loci, those of depth >= 1 (observed), the sum of their depths (hits) and the largest. */
 #define SPEQ_MARKER_BINS 8
 typedef struct {
     uint64_t markers, observed, hits, max_depth, depth_hist[SPEQ_MARKER_BINS];
@@ -233,6 +242,20 @@ int speq_markers_finalize(speq_markers* m, speq_marker_cov* out);
  * number; lo / group / depth (any may be NULL) hold that many entries each: call once with null arrays for the size. */
 int speq_markers_list(speq_markers* m, uint64_t* n_markers, uint32_t* lo, uint32_t* group, uint32_t* depth);
 void speq_markers_free(speq_markers* m);
+typedef struct {
+    uint64_t markers, observed, hits, max_depth;
+} speq_marker_bin; /* 32 bytes */
+#define SPEQ_TRACK_MAX_BIN (1u << 20)
+/* Host only: the bins per record as a prefix, first_bin[R + 1] for the index's R records (may be NULL for the size
+ * alone); *n_bins (may be NULL) = first_bin[R]. 1 <= bin <= SPEQ_TRACK_MAX_BIN. The second form needs no replica:
+ * the same layout from an index and a scan length (1 .. SPEQ_REPORT_MAX_K). */
+int speq_markers_track_layout(const speq_markers* m, uint32_t bin, uint64_t* n_bins, uint64_t* first_bin);
+int speq_index_track_layout(const speq_index* idx, uint32_t k, uint32_t bin, uint64_t* n_bins, uint64_t* first_bin);
+/* Waits for the adds of every stream of the device (as speq_markers_finalize does), runs one pass over the forward
+ * texts and overwrites out[n_bins] (host), record after record as the layout says. Reads the handle's depths and
+ * changes nothing of it: the handle stays usable, more adds and another track give the totals so far, and
+ * speq_markers_finalize returns the same records before and after. SPEQ_E_NOMEM when the bins do not fit the free HBM. */
+int speq_markers_track(speq_markers* m, uint32_t bin, speq_marker_bin* out);
 
 /* ---- read bootstrap: how far to trust a percentage (a diagnostic pass beside the scan) ----
  * The scan's counter vector under B Poisson(1) resamplings of the reads, in one pass. The resampling unit is the read,
@@ -520,6 +543,12 @@ void speq_group_sets_free(speq_group_sets* s);
  * blocks parsed on host threads and added in any order, one finalize at the end into out[G]. stats may be NULL. */
 int speq_markers_fastq(speq_device_index* d, const char* path1, const char* path2, const speq_scan_params* params,
                        uint32_t threads, speq_marker_cov* out, speq_stream_stats* stats);
+/* The same single pass over the file(s), and both answers from its handle: cov[G] as speq_markers_fastq gives (cov may
+ * be NULL), and the marker track at width `bin` (speq_markers_track): first_bin[R + 1] (the caller's, R = the index's
+ * records) and *out, *n_bins records allocated here and freed with speq_free (NULL when there is no bin). */
+int speq_markers_track_fastq(speq_device_index* d, const char* path1, const char* path2, const speq_scan_params* params,
+                             uint32_t threads, uint32_t bin, speq_marker_cov* cov, uint64_t* first_bin,
+                             speq_marker_bin** out, uint64_t* n_bins, speq_stream_stats* stats);
 
 /* The read bootstrap (speq_bootstrap_*) of the whole of FASTQ file(s) (plain or gzip; paired when path2 != NULL)
  * through a handle of its own: blocks parsed on host threads and added in any order, each with the index of its first

@@ -62,6 +62,13 @@ class MarkerCov(C.Structure):
                 ("depth_hist", C.c_uint64 * MARKER_BINS)]
 
 
+TRACK_MAX_BIN = 1 << 20
+
+
+class MarkerBin(C.Structure):
+    _fields_ = [("markers", C.c_uint64), ("observed", C.c_uint64), ("hits", C.c_uint64), ("max_depth", C.c_uint64)]
+
+
 BOOTSTRAP_MAX_REPLICATES = 1024
 
 
@@ -116,6 +123,11 @@ SIGNATURES = {
     "speq_markers_fastq": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.POINTER(ScanParams), C.c_uint32, _P,
                                      C.POINTER(StreamStats)]),
     "speq_markers_free": (None, [_P]),
+    "speq_markers_track_layout": (C.c_int, [_P, C.c_uint32, _U64P, _U64P]),
+    "speq_index_track_layout": (C.c_int, [_P, C.c_uint32, C.c_uint32, _U64P, _U64P]),
+    "speq_markers_track": (C.c_int, [_P, C.c_uint32, _P]),
+    "speq_markers_track_fastq": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.POINTER(ScanParams), C.c_uint32, C.c_uint32,
+                                           _P, _U64P, C.POINTER(_P), _U64P, C.POINTER(StreamStats)]),
     "speq_bootstrap_create": (C.c_int, [_P, C.POINTER(ScanParams), C.c_uint32, C.c_uint64, C.POINTER(_P)]),
     "speq_bootstrap_add_reads_device": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_uint64, _P]),
     "speq_bootstrap_add_reads": (C.c_int, [_P, C.c_char_p, C.c_char_p, _U64P, C.c_uint64, C.c_uint64]),

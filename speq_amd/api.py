@@ -23,7 +23,7 @@ import numpy as np
 from ._lib import (MARKER_BINS, SPEQ_MODE_GLOBAL, SPEQ_MODE_LOCAL, BootstrapCI, BuildOpts, IndexInfo,  # noqa: F401
                    DedupStatsRecord, ScanParams, Slot, SpeqError, StreamStats, check, lib)
 
-__all__ = ["FmIndex", "DeviceIndex", "Node", "Pipeline", "ScanResult", "ReadReport", "Markers", "MarkerCoverage", "Bootstrap",
+__all__ = ["FmIndex", "DeviceIndex", "Node", "Pipeline", "ScanResult", "ReadReport", "Markers", "MarkerCoverage", "MarkerTrack", "Bootstrap",
            "Dedup", "DedupStats", "dedup_fingerprint", "bootstrap_summary", "bootstrap_summary_percent", "em_rows_step", "em_rows_refine", "Groupings", "EmHistogram", "Comm", "file_to_map", "unique_to_percent",
            "em_refine", "pack_records", "SpeqError", "SPEQ_MODE_GLOBAL", "SPEQ_MODE_LOCAL"]
 
@@ -147,6 +147,16 @@ class FmIndex:
             return np.zeros(0, dtype=dtype)
         return np.frombuffer(C.string_at(p, nb.value), dtype=dtype).copy()
 
+    def track_layout(self, k: int, bin: int = 100) -> np.ndarray:
+        """first_bin[R + 1] of the marker track at scan length k (speq_index_track_layout; host only)."""
+        first = np.zeros(self.info().n_records + 1, dtype=np.uint64)
+        check(lib().speq_index_track_layout(self._h, k, bin, None, _u64p(first)))
+        return first
+
+    def track_loci(self, k: int) -> np.ndarray:
+        """Loci per record at scan length k: the bins of width 1."""
+        return np.diff(self.track_layout(k, 1))
+
     @property
     def handle(self):
         return self._h
@@ -212,6 +222,52 @@ class MarkerCoverage:
         """1 - exp(-hits / markers): the breadth that uniform sampling at this depth would give; the figure to hold
         `breadth` against (nan for a group without markers)."""
         return 1.0 - np.exp(-self.mean_depth)
+
+
+TRACK_DTYPE = np.dtype([("markers", np.uint64), ("observed", np.uint64), ("hits", np.uint64), ("max_depth", np.uint64)])
+
+
+@dataclass
+class MarkerTrack:
+    """The marker track (speq_markers_track): per record, bins of `bin` loci (window starts of the forward text), and
+    per bin the marker loci, those covered, the sum of their depths and the largest. A locus's depth is its k-mer's
+    plus its reverse complement's (once when the two are one k-mer)."""
+    first_bin: np.ndarray    # [R + 1] uint64: record r's rows are bins[first_bin[r]:first_bin[r + 1]]
+    bins: np.ndarray         # structured (TRACK_DTYPE), one row per bin, record after record
+    bin: int
+    k: int
+    loci: np.ndarray         # [R] uint64: loci of each record, max(len - k + 1, 0)
+
+    @property
+    def n_records(self) -> int:
+        return len(self.first_bin) - 1
+
+    def record(self, r: int) -> np.ndarray:
+        """The rows of record r (none for a record shorter than k)."""
+        return self.bins[int(self.first_bin[r]):int(self.first_bin[r + 1])]
+
+    def start(self, r: int, b: int) -> int:
+        """First locus of bin b of record r."""
+        if not 0 <= b < len(self.record(r)):
+            raise IndexError(f"record {r} has no bin {b}")
+        return b * self.bin
+
+    def end(self, r: int, b: int) -> int:
+        """One past the last locus of bin b of record r."""
+        if not 0 <= b < len(self.record(r)):
+            raise IndexError(f"record {r} has no bin {b}")
+        return min((b + 1) * self.bin, int(self.loci[r]))
+
+    def breadth(self) -> np.ndarray:
+        """observed / markers per bin (nan for a bin without marker loci)."""
+        m = self.bins["markers"]
+        with np.errstate(all="ignore"):
+            return np.where(m > 0, self.bins["observed"] / np.maximum(m, 1).astype(np.float64), np.nan)
+
+    def mean_depth(self) -> np.ndarray:
+        m = self.bins["markers"]
+        with np.errstate(all="ignore"):
+            return np.where(m > 0, self.bins["hits"] / np.maximum(m, 1).astype(np.float64), np.nan)
 
 
 @dataclass
@@ -328,6 +384,22 @@ class DeviceIndex:
         check(lib().speq_markers_fastq(self._h, path1.encode(), path2.encode() if path2 else None, C.byref(p), threads,
                                        rec.ctypes.data, None))
         return MarkerCoverage.from_records(rec)
+
+    def marker_track_fastq(self, path1: str, path2: Optional[str] = None, k: int = 21, phred_cutoff: int = 30,
+                           bin: int = 100, threads: int = 4) -> tuple[MarkerCoverage, "MarkerTrack"]:
+        """Marker coverage and the marker track of FASTQ(.gz) file(s) from one pass (speq_markers_track_fastq)."""
+        p = ScanParams(k, phred_cutoff, int(path2 is not None), SPEQ_MODE_GLOBAL)
+        rec = np.zeros((self.n_groups, 4 + MARKER_BINS), dtype=np.uint64)
+        first = np.zeros(self.index.info().n_records + 1, dtype=np.uint64)
+        rows, n = C.c_void_p(), C.c_uint64()
+        check(lib().speq_markers_track_fastq(self._h, path1.encode(), path2.encode() if path2 else None, C.byref(p),
+                                             threads, bin, rec.ctypes.data, _u64p(first), C.byref(rows), C.byref(n), None))
+        try:
+            bins = np.frombuffer(C.string_at(rows, n.value * TRACK_DTYPE.itemsize), dtype=TRACK_DTYPE).copy() \
+                if n.value else np.zeros(0, dtype=TRACK_DTYPE)
+        finally:
+            lib().speq_free(rows)
+        return MarkerCoverage.from_records(rec), MarkerTrack(first, bins, bin, k, self.index.track_loci(k))
 
     def bootstrap(self, seq: bytes, qual: bytes, offsets: np.ndarray, k: int, replicates: int = 200, seed: int = 1,
                   phred_cutoff: int = 30, paired: bool = False, local: bool = False, first_unit: int = 0):
@@ -507,6 +579,7 @@ class Markers:
     def __init__(self, dev: DeviceIndex, k: int, phred_cutoff: int = 30):
         self.dev = dev
         self.n_groups = dev.n_groups
+        self.k = k
         p = ScanParams(k, phred_cutoff, 0, SPEQ_MODE_GLOBAL)
         h = C.c_void_p()
         check(lib().speq_markers_create(dev.handle, C.byref(p), C.byref(h)))
@@ -525,6 +598,16 @@ class Markers:
         rec = np.zeros((self.n_groups, 4 + MARKER_BINS), dtype=np.uint64)
         check(lib().speq_markers_finalize(self._h, rec.ctypes.data))
         return MarkerCoverage.from_records(rec)
+
+    def track(self, bin: int = 100) -> MarkerTrack:
+        """The marker track of everything added so far (speq_markers_track); the handle stays usable."""
+        first = np.zeros(self.dev.index.info().n_records + 1, dtype=np.uint64)
+        n = C.c_uint64()
+        check(lib().speq_markers_track_layout(self._h, bin, C.byref(n), _u64p(first)))
+        bins = np.zeros(n.value, dtype=TRACK_DTYPE)
+        if n.value:
+            check(lib().speq_markers_track(self._h, bin, bins.ctypes.data))
+        return MarkerTrack(first, bins, bin, self.k, self.dev.index.track_loci(self.k))
 
     def list(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Test accessor (speq_markers_list): (lo, group, depth) of every marker, ascending SA position."""

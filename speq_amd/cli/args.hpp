@@ -38,6 +38,9 @@ struct CmdArguments {  // include/arg_parse.h:10-28
     unsigned int max_em_iterations{1000};
     std::filesystem::path out_file_group_sets{};  // --group-sets: the pairs' (reads') group sets, the real fusion map
     std::filesystem::path out_file_marker_coverage{};  // --marker-coverage: per group, its markers and their depths
+    std::filesystem::path out_file_marker_track{};  // --marker-track: per record and bin, where the covered markers lie
+    unsigned int track_bin{100};                  // --track-bin: loci per bin
+    bool track_bin_given{false};
     std::filesystem::path out_file_bootstrap{};   // --bootstrap: per group, the percentage and its bootstrap interval
     std::filesystem::path out_file_bootstrap_em{};  // --bootstrap-em: the same for the EM-refined percentages
     unsigned int bootstrap_replicates{200};       // --bootstrap-replicates

@@ -63,6 +63,12 @@ const char* HELP =
     "                            its unique k-mers (markers) the reads cover and how deep: name, markers, observed,\n"
     "                            breadth, hits, mean_depth, expected_breadth, max_depth, d0..d7 (tab-separated); a\n"
     "                            breadth far below expected_breadth means copies of few k-mers, not the variant\n"
+    "      --marker-track FILE   scan: after the scan, one more pass over the reads (the same one as --marker-coverage's\n"
+    "                            when both are given) writes FILE: per reference record and bin of --track-bin window\n"
+    "                            starts, where the covered markers lie: record (0-based, FASTA order), group, start,\n"
+    "                            end, markers, observed, breadth, hits, mean_depth, max_depth (tab-separated); both\n"
+    "                            strands of a k-mer count at its place in the record\n"
+    "      --track-bin N         window starts per bin of --marker-track, 1..1048576 (default 100)\n"
     "      --bootstrap FILE      scan: after the scan, one more pass over the reads resamples them (Poisson bootstrap\n"
     "                            of the reads, or pairs) and writes FILE: name, percent, mean, se, lo, hi, used\n"
     "                            (tab-separated): the interval of each group's initial percentage, the first vector\n"
@@ -175,6 +181,11 @@ CmdArguments parse(int argc, char** argv) {
         }
         else if (allow_reads && opt == "--group-sets") a.out_file_group_sets = value();
         else if (allow_reads && opt == "--marker-coverage") a.out_file_marker_coverage = value();
+        else if (allow_reads && opt == "--marker-track") a.out_file_marker_track = value();
+        else if (allow_reads && opt == "--track-bin") {
+            a.track_bin = to_number<unsigned>(opt, value());
+            a.track_bin_given = true;
+        }
         else if (allow_reads && opt == "--bootstrap") a.out_file_bootstrap = value();
         else if (allow_reads && opt == "--bootstrap-em") a.out_file_bootstrap_em = value();
         else if (allow_reads && opt == "--bootstrap-replicates") a.bootstrap_replicates = to_number<unsigned>(opt, value());
@@ -201,6 +212,11 @@ CmdArguments parse(int argc, char** argv) {
     if (!(a.bootstrap_level > 0.0 && a.bootstrap_level < 1.0))
         throw ParseError("Validation failed for option --bootstrap-level: Value " + std::to_string(a.bootstrap_level) +
                          " is not in range (0,1).");
+    if (a.track_bin < 1 || a.track_bin > SPEQ_TRACK_MAX_BIN)
+        throw ParseError("Validation failed for option --track-bin: Value " + std::to_string(a.track_bin) +
+                         " is not in range [1," + std::to_string(SPEQ_TRACK_MAX_BIN) + "].");
+    if (a.track_bin_given && a.out_file_marker_track.empty())
+        throw ParseError("Option --track-bin needs --marker-track FILE.");
     if (a.prefix_q > 13) throw ParseError("Validation failed for option --prefix-q: must be <= 13");
     if (a.is_scanner) {
         check_in_file(a.in_file_reads_path_1);
@@ -222,6 +238,7 @@ CmdArguments parse(int argc, char** argv) {
     check_out_file(a.out_file_path, a.is_force);
     if (!a.out_file_group_sets.empty()) check_out_file(a.out_file_group_sets, a.is_force);
     if (!a.out_file_marker_coverage.empty()) check_out_file(a.out_file_marker_coverage, a.is_force);
+    if (!a.out_file_marker_track.empty()) check_out_file(a.out_file_marker_track, a.is_force);
     if (!a.out_file_bootstrap.empty()) check_out_file(a.out_file_bootstrap, a.is_force);
     if (!a.out_file_bootstrap_em.empty()) check_out_file(a.out_file_bootstrap_em, a.is_force);
     if (!a.out_file_dedup.empty()) check_out_file(a.out_file_dedup, a.is_force);
@@ -557,13 +574,67 @@ void write_group_sets(const CmdArguments& a, speq_device_index* d, const speq_sc
 // FILE of --marker-coverage: a header line, then per group (groupings order) its name, markers, observed,
 // breadth = observed / markers, hits, mean_depth = hits / markers, expected_breadth = 1 - exp(-mean_depth) (the breadth
 // uniform sampling at that depth would give), max_depth and the eight depth bins; the ratios are "-" without markers.
-void write_marker_coverage(const CmdArguments& a, speq_device_index* d, const speq_scan_params& prm,
-                           const std::vector<std::string>& names) {
+//
+// FILE of --marker-track: a header line, then per record (FASTA order) one line per bin of --track-bin loci: the
+// record's number, its group's name, the bin's first locus and one past its last, markers, observed, breadth, hits,
+// mean_depth, max_depth. When both files are asked for, one pass over the reads serves both.
+struct MarkerTrackRows {
+    std::vector<uint64_t> first_bin;  // [R + 1]
+    speq_marker_bin* rows = nullptr;  // the library's, freed with speq_free
+    ~MarkerTrackRows() { speq_free(rows); }
+};
+
+std::string ratio6(double x) {
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "%.6f", x);
+    return std::string(buf);
+}
+
+void write_marker_track(const CmdArguments& a, const speq_index* idx, const MarkerTrackRows& t,
+                        const std::vector<std::string>& names) {
+    const void* tg = nullptr;
+    uint64_t tg_bytes = 0, nwin_total = 0;
+    ok(speq_index_array(idx, "text_group", &tg, &tg_bytes), "reading the index");
+    const int32_t* text_group = static_cast<const int32_t*>(tg);
+    const uint32_t n_rec = (uint32_t)(t.first_bin.size() - 1);
+    std::vector<uint64_t> first_locus(n_rec + 1);  // the layout at bin 1: the loci per record
+    ok(speq_index_track_layout(idx, a.kmer, 1, &nwin_total, first_locus.data()), "marker track");
+    std::ofstream of(a.out_file_marker_track);
+    if (!of) throw CApiError("cannot write " + a.out_file_marker_track.string());
+    of << "record\tgroup\tstart\tend\tmarkers\tobserved\tbreadth\thits\tmean_depth\tmax_depth\n";
+    for (uint32_t r = 0; r < n_rec; ++r) {
+        const uint64_t loci = first_locus[r + 1] - first_locus[r];
+        const std::string& group = names[(size_t)text_group[2 * (size_t)r]];
+        for (uint64_t i = t.first_bin[r]; i < t.first_bin[r + 1]; ++i) {
+            const speq_marker_bin& c = t.rows[i];
+            const uint64_t start = (i - t.first_bin[r]) * a.track_bin;
+            const bool has = c.markers > 0;
+            of << r << "\t" << group << "\t" << start << "\t" << std::min<uint64_t>(start + a.track_bin, loci) << "\t"
+               << c.markers << "\t" << c.observed << "\t"
+               << (has ? ratio6((double)c.observed / (double)c.markers) : std::string("-")) << "\t" << c.hits << "\t"
+               << (has ? ratio6((double)c.hits / (double)c.markers) : std::string("-")) << "\t" << c.max_depth << "\n";
+        }
+    }
+}
+
+void write_marker_coverage(const CmdArguments& a, const speq_index* idx, speq_device_index* d,
+                           const speq_scan_params& prm, const std::vector<std::string>& names, MarkerTrackRows* track) {
     std::vector<speq_marker_cov> cov(names.size());
-    ok(speq_markers_fastq(d, a.in_file_reads_path_1.c_str(),
-                          a.in_file_reads_path_2.empty() ? nullptr : a.in_file_reads_path_2.c_str(), &prm, a.threads,
-                          cov.data(), nullptr),
-       "marker coverage");
+    const char* p1 = a.in_file_reads_path_1.c_str();
+    const char* p2 = a.in_file_reads_path_2.empty() ? nullptr : a.in_file_reads_path_2.c_str();
+    if (track) {
+        speq_index_info info{};
+        ok(speq_index_get_info(idx, &info), "reading the index");
+        track->first_bin.assign((size_t)info.n_records + 1, 0);
+        uint64_t n_bins = 0;
+        ok(speq_markers_track_fastq(d, p1, p2, &prm, a.threads, a.track_bin,
+                                    a.out_file_marker_coverage.empty() ? nullptr : cov.data(), track->first_bin.data(),
+                                    &track->rows, &n_bins, nullptr),
+           "marker track");
+    } else {
+        ok(speq_markers_fastq(d, p1, p2, &prm, a.threads, cov.data(), nullptr), "marker coverage");
+    }
+    if (a.out_file_marker_coverage.empty()) return;
     std::ofstream of(a.out_file_marker_coverage);
     if (!of) throw CApiError("cannot write " + a.out_file_marker_coverage.string());
     of << "name\tmarkers\tobserved\tbreadth\thits\tmean_depth\texpected_breadth\tmax_depth";
@@ -985,9 +1056,16 @@ int run_scan(CmdArguments& a) {
     }
     // --marker-coverage: one more pass over the same reads, placed like --group-sets (first replica, whole file, after
     // everything else the run prints and writes).
-    if (!a.out_file_marker_coverage.empty()) {
-        write_marker_coverage(a, d, prm, h.names);
-        phase("marker coverage");
+    // --marker-track rides on the same pass: one stream of the reads fills the handle that both files are folded from.
+    if (!a.out_file_marker_coverage.empty() || !a.out_file_marker_track.empty()) {
+        MarkerTrackRows track;
+        const bool want_track = !a.out_file_marker_track.empty();
+        write_marker_coverage(a, idx, d, prm, h.names, want_track ? &track : nullptr);
+        if (!a.out_file_marker_coverage.empty()) phase("marker coverage");
+        if (want_track) {
+            write_marker_track(a, idx, track, h.names);
+            phase("marker track");
+        }
     }
     // --bootstrap / --bootstrap-em: one more pass over the same reads, placed like --group-sets; mode, pairing, k,
     // cutoff and the fixed accuracy are the run's own. --bootstrap's intervals bound the initial percentages (the first

@@ -1645,6 +1645,46 @@ extern "C" int speq_markers_fastq(speq_device_index* d, const char* path1, const
     return rc;
 }
 
+// The same stream into one handle, then both folds of its depths: per group (when cov is given) and per bin of every
+// record. The bins' array is allocated once their number is known and handed over only when everything went through.
+extern "C" int speq_markers_track_fastq(speq_device_index* d, const char* path1, const char* path2,
+                                        const speq_scan_params* params, uint32_t threads, uint32_t bin,
+                                        speq_marker_cov* cov, uint64_t* first_bin, speq_marker_bin** out,
+                                        uint64_t* n_bins, speq_stream_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const char* who = "speq_markers_track_fastq";
+    int rc = speq::guarded([&] {
+        if (!params) throw std::invalid_argument(std::string(who) + ": null params");
+        speq::check_report_k(who, params->k);
+        if (!d || !path1 || !first_bin || !out || !n_bins) throw std::invalid_argument(std::string(who) + ": null argument");
+        speq::check_track_bin(who, bin);
+    });
+    if (rc != SPEQ_OK) return rc;
+    speq_markers* m = nullptr;
+    rc = speq_markers_create(d, params, &m);
+    if (rc != SPEQ_OK) return rc;
+    speq_marker_bin* rows = nullptr;
+    rc = speq::guarded([&] {
+        MarkerSink sink(m);
+        const StreamTotals tot = run_stream(path1, path2, threads, sink, false, false);
+        if (cov) check_rc(speq_markers_finalize(m, cov));
+        uint64_t nb = 0;
+        check_rc(speq_markers_track_layout(m, bin, &nb, first_bin));
+        if (nb) {
+            rows = static_cast<speq_marker_bin*>(std::malloc(nb * sizeof(speq_marker_bin)));
+            if (!rows) throw std::bad_alloc();
+            check_rc(speq_markers_track(m, bin, rows));
+        }
+        *out = rows;
+        *n_bins = nb;
+        rows = nullptr;
+        fill_stats(stats, tot, t0);
+    });
+    std::free(rows);
+    speq_markers_free(m);
+    return rc;
+}
+
 // speq_bootstrap_fastq, and with em != NULL speq_bootstrap_em_fastq: the same stream into a handle with the histogram
 // attached
 static int bootstrap_fastq_impl(const char* who, speq_device_index* d, const speq_em* em, const char* path1,

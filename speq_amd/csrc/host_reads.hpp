@@ -37,4 +37,10 @@ inline void check_report_k(const char* who, uint32_t k) {
         throw std::invalid_argument(std::string(who) + ": k must be in [1, " + std::to_string(SPEQ_REPORT_MAX_K) + "]");
 }
 
+// the bin width of the marker track
+inline void check_track_bin(const char* who, uint32_t bin) {
+    if (bin < 1 || bin > SPEQ_TRACK_MAX_BIN)
+        throw std::invalid_argument(std::string(who) + ": bin must be in [1, " + std::to_string(SPEQ_TRACK_MAX_BIN) + "]");
+}
+
 }  // namespace speq

@@ -14,21 +14,13 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "markers_handle.hpp"
 #include "window_pass.hpp"
-
-struct speq_markers {
-    speq_device_index* dev = nullptr;
-    speq_scan_params params{};  // k and phred_cutoff, fixed at create
-    uint64_t n = 0;             // SA positions
-    uint32_t G = 0;
-    speq_dev::DevPtr<uint32_t> d_depth;  // [n]: MARK | depth
-};
 
 namespace {
 
 using namespace speq_dev;
 
-constexpr uint32_t MARK = 0x80000000u;        // bit 31 of a depth word: the position starts a marker's interval
 constexpr uint32_t LDS_TALLY_GROUPS = 512u;   // the fold tallies in LDS up to this many groups (26 KiB), else in HBM
 constexpr uint32_t COV_WORDS = sizeof(speq_marker_cov) / 8;  // u64 words of one group's record
 // per-block tally of the fold, per group: u64 hits, then u32 {markers, observed, max_depth, bins[8]}

@@ -1,6 +1,7 @@
 // What the diagnostic window passes beside the scan kernels share (per-unit report, read_report.hip, DESIGN.md §4n;
-// marker coverage, read_markers.hip, §4o): every passing window of a tile of 64 window starts gets an exact backward
-// search, and host reads reach the device in staged batches. Each pass keeps its kernels in its own translation unit.
+// marker coverage, read_markers.hip, §4o; marker track, marker_track.hip, §4t): every passing window of a tile of 64
+// window starts gets an exact backward search, and host reads reach the device in staged batches. Each pass keeps its
+// kernels in its own translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
 
