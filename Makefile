@@ -88,6 +88,8 @@ AXKNOB_kv3 := -DSPEQ_AX_SPEC_HW=1 -DSPEQ_AX_PRIO=0 -DSPEQ_AX_MPROOF=0
 AXKNOB_kv4 := -DSPEQ_AX_SPROOF=0
 # (kv3 also stages every batch with all its stream instructions)
 AXKNOB_kv3 += -DSPEQ_AX_STAGE_SKIP=0
+# (... and keeps phase 1's guarded slot reads, per-dword first mismatch and 8-dword finish_piece)
+AXKNOB_kv3 += -DSPEQ_AX_LEAN=0
 AXKNOBS    := kv1 kv2 kv3 kv4
 AXKNOB_OTHER := $(filter-out $(OBJDIR)/ax_scan.o,$(LIB_OBJS))
 

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "ax_decode.hpp"
+#include "ax_phase1.hpp"
 #include "scan_device.hpp"
 #include "speq_scan.h"
 
@@ -38,13 +39,21 @@ namespace {
 using namespace speq_dev;
 
 // Compile-time knobs (A/B only; every one is run through the parity tests forced to a non-default value by
-// tests/test_gpu_ax_knobs.py and tests/test_gpu_sproof_knob.py over `make axknobs` builds), eighteen: SPEQ_AX_STAGE_SKIP, SPEQ_AX_DEF_LOCAL, SPEQ_AX_DEF_GLOBAL, SPEQ_AX_WL,
+// tests/test_gpu_ax_knobs.py and tests/test_gpu_sproof_knob.py over `make axknobs` builds), nineteen: SPEQ_AX_LEAN, SPEQ_AX_STAGE_SKIP, SPEQ_AX_DEF_LOCAL, SPEQ_AX_DEF_GLOBAL, SPEQ_AX_WL,
 // SPEQ_AX_WPB, SPEQ_AX_SU, SPEQ_AX_SU_LOCAL, SPEQ_AX_MIN_WAVES, SPEQ_AX_MIN_WAVES_LOCAL, SPEQ_AX_REFILL, SPEQ_AX_BLOCKED,
 // SPEQ_AX_SPEC_HW, SPEQ_AX_PRIO, SPEQ_AX_PRIO_MIN, SPEQ_AX_P2_MARGIN, SPEQ_AX_MPROOF, SPEQ_AX_MTILES, SPEQ_AX_SPROOF.
 // Measured losers
 // of rounds 3-5 (a cuckoo anchor table, lowest / first-claimant representatives, a dynamic tail, generation-weighted
 // pools, offset prefetch, speculative runs in global mode, a minimizer-keyed filter, workgroup-shared pools) were
 // removed; DESIGN.md §4f-§4g keep their numbers.
+#if !defined(SPEQ_AX_LEAN)  // (described with the staging knobs below)
+#define SPEQ_AX_LEAN 1
+#endif
+// its items: 1 = all, 0 = none; 2 x (a set of bits) = single items, for the A/B builds of DESIGN.md §4u
+constexpr uint32_t AX_LEAN_ITEMS = SPEQ_AX_LEAN == 1 ? 7u : (uint32_t)(SPEQ_AX_LEAN) >> 1;
+constexpr bool AX_LEAN_READS = (AX_LEAN_ITEMS & 1u) != 0;    // unguarded reads of a lane's own slot
+constexpr bool AX_LEAN_MISMATCH = (AX_LEAN_ITEMS & 2u) != 0; // a run's first mismatch in one pass
+constexpr bool AX_LEAN_PIECE = (AX_LEAN_ITEMS & 4u) != 0;    // finish_piece on 6 dwords where the group allows
 constexpr uint32_t AX_MAX_K = 128;    // longest k the scan takes (AX_CAP - k + 1 windows per segment)
 constexpr uint32_t AX_CAP = 192;      // bases of a read a lane stages at once (longer reads: segments of AX_CAP bases)
 constexpr uint32_t AX_STREAM = AX_CAP + 16;  // staged bases incl. the 16-B alignment slack before the read
@@ -285,6 +294,12 @@ static_assert(AX_WL % 64u == 0 && AX_WL >= 64u && AX_WL <= 512u, "work list: 1-8
 #if !defined(SPEQ_AX_STAGE_SKIP)
 #define SPEQ_AX_STAGE_SKIP 1
 #endif
+// SPEQ_AX_LEAN 1: phase 1 and finish_piece without the instructions the result does not need: a lane's
+// reads of its own slot carry no bounds guard (a later clamp or mask discards what lies past the piece, and the
+// furthest byte stays inside the wave's LDS: the static_asserts in k_scan_ax), a run's first mismatch takes one pass
+// (ax_phase1.hpp), and finish_piece works on the 6 dwords a group of pieces of at most 11 chunks has; 0: the code as
+// it was (A/B switch; forced to 0 in the `kv3` build of `make axknobs`, so the knob suite keeps running that path;
+// defined above, with its items)
 template <int MODE, bool PAIRED, int HW>
 constexpr uint32_t ax_su() {
     return MODE == KM_LOCAL ? SPEQ_AX_SU_LOCAL

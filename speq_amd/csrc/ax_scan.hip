@@ -463,29 +463,64 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
         if (LDS_HIST) atomicAdd(&hW[g], w);
         else atomicAdd(&out_w[g], w);
     };
+    // (LEAN) A lane's phase-1 reads of its own slot carry no bounds guard: what lies past the piece is
+    // discarded later (ax_hash masks to k or m bases, a run clamps its first mismatch to cl and masks its windows to
+    // R, the valid-bit searches stop at the piece's last window), so a guard only has to keep the address inside the
+    // wave's LDS. Furthest bytes, from the wave's base: code rows up to AX_CHUNKS - 1 (a clamp: the row does not
+    // depend on j of a lane that is not working) + 2 AX_CMPW further ones (a run's AX_CMP bases at any shift; the
+    // words of a k-mer need 2 HW <= 8), valid-window dwords up to (AX_CAP - 1) / 32 + AX_CMPW (a run) and 64-bit
+    // words up to (AX_CAP - 1 + 64) / 64 + 1 (a deferral's second mask). The last wave's region ends with the
+    // workgroup's LDS (scan_plan.hpp: lds_bytes). Phase 2 reads other lanes' slots at positions from list entries
+    // (AX_EMPTY: above 1,023) and keeps its guards.
+    constexpr bool LEAN = AX_LEAN_READS;
+    constexpr uint32_t AX_VW_BASE = 4u * AX_CHUNKS * 64u;  // bytes of the code rows before the valid-window words
+    static_assert(HW >= 1 && HW <= 4 && 2u * (uint32_t)HW <= 2u * AX_CMPW, "a k-mer's words: 2 HW + 1 code rows");
+    static_assert(4u * 64u * (AX_CHUNKS + 2u * AX_CMPW) <= ax_wave_bytes<KM_GLOBAL>() &&
+                      4u * 64u * (AX_CHUNKS + 2u * AX_CMPW) <= ax_wave_bytes<KM_LOCAL>(),
+                  "unguarded code rows (AX_CHUNKS - 1) + 0 .. 2 AX_CMPW end inside the wave's LDS");
+    static_assert(AX_VW_BASE + 8u * 64u * (((AX_CAP - 1u) / 32u + AX_CMPW) / 2u + 1u) <= ax_wave_bytes<KM_GLOBAL>() &&
+                      AX_VW_BASE + 8u * 64u * (((AX_CAP - 1u) / 32u + AX_CMPW) / 2u + 1u) <= ax_wave_bytes<KM_LOCAL>(),
+                  "unguarded valid-window dwords of a run end inside the wave's LDS");
+    static_assert(AX_VW_BASE + 8u * 64u * ((AX_CAP - 1u + 64u) / 64u + 2u) <= ax_wave_bytes<KM_GLOBAL>() &&
+                      AX_VW_BASE + 8u * 64u * ((AX_CAP - 1u + 64u) / 64u + 2u) <= ax_wave_bytes<KM_LOCAL>(),
+                  "unguarded valid-window words of a deferral end inside the wave's LDS");
+    using own_t = std::bool_constant<LEAN>;     // a lane's own slot at a position inside its piece
+    using other_t = std::false_type;            // any slot, any position: guarded
     // 32 bases (64 bits) of slot o from slot position pos
-    auto slot64 = [&](uint32_t o, uint32_t pos) -> uint64_t {
+    auto slot64 = [&](auto own, uint32_t o, uint32_t pos) -> uint64_t {
+        if constexpr (decltype(own)::value) {
+            const uint32_t d = min(pos >> 4, AX_CHUNKS - 1u), sh = 2u * (pos & 15u);
+            const uint32_t w0 = codes[d * 64u + o], w1 = codes[(d + 1u) * 64u + o], w2 = codes[(d + 2u) * 64u + o];
+            return u64of(alignbit(w1, w0, sh), alignbit(w2, w1, sh));
+        }
         const uint32_t d = pos >> 4, sh = 2u * (pos & 15u);
         const uint32_t w0 = d < AX_CHUNKS ? codes[d * 64u + o] : 0u;
         const uint32_t w1 = d + 1u < AX_CHUNKS ? codes[(d + 1u) * 64u + o] : 0u;
         const uint32_t w2 = d + 2u < AX_CHUNKS ? codes[(d + 2u) * 64u + o] : 0u;
         return u64of(alignbit(w1, w0, sh), alignbit(w2, w1, sh));
     };
-    auto read_words = [&](uint32_t o, uint32_t pos, uint64_t(&w)[HW]) {  // HW code words of slot o at pos
+    auto read_words = [&](auto own, uint32_t o, uint32_t pos, uint64_t(&w)[HW]) {  // HW code words of slot o at pos
         if (HW <= 2) {  // (HW = 2: the shared reads below hold more registers at once and spill)
 #pragma unroll
-            for (int i = 0; i < HW; ++i) w[i] = slot64(o, pos + 32u * (uint32_t)i);
+            for (int i = 0; i < HW; ++i) w[i] = slot64(own, o, pos + 32u * (uint32_t)i);
             return;
         }
         // the 2 HW + 1 slot words that cover them, each read once (consecutive 64-bit words share a slot word)
-        const uint32_t d = pos >> 4, sh = 2u * (pos & 15u);
+        constexpr bool OWN = decltype(own)::value;
+        const uint32_t d = OWN ? min(pos >> 4, AX_CHUNKS - 1u) : pos >> 4, sh = 2u * (pos & 15u);
         uint32_t c[2 * HW + 1];
 #pragma unroll
-        for (int i = 0; i <= 2 * HW; ++i) c[i] = d + (uint32_t)i < AX_CHUNKS ? codes[(d + (uint32_t)i) * 64u + o] : 0u;
+        for (int i = 0; i <= 2 * HW; ++i)
+            c[i] = (OWN || d + (uint32_t)i < AX_CHUNKS) ? codes[(d + (uint32_t)i) * 64u + o] : 0u;
 #pragma unroll
         for (int i = 0; i < HW; ++i) w[i] = u64of(alignbit(c[2 * i + 1], c[2 * i], sh), alignbit(c[2 * i + 2], c[2 * i + 1], sh));
     };
-    auto vbits = [&](uint32_t o, uint32_t b) -> uint64_t {  // read o's valid-window bits b .. b + 63 (0 past the end)
+    // read o's valid-window bits b .. b + 63 (0 past the end; own: bits from window 64 AX_VWW on are not defined)
+    auto vbits = [&](auto own, uint32_t o, uint32_t b) -> uint64_t {
+        if constexpr (decltype(own)::value) {
+            const uint32_t w0 = min(b >> 6, AX_VWW - 1u), s6 = b & 63u;
+            return funnel(vw[w0 * 64u + o], vw[(w0 + 1u) * 64u + o], s6);
+        }
         const uint32_t w0 = b >> 6, s6 = b & 63u;
         const uint64_t lo = w0 < AX_VWW ? vw[w0 * 64u + o] : 0ull;
         const uint64_t hi = w0 + 1u < AX_VWW ? vw[(w0 + 1u) * 64u + o] : 0ull;
@@ -493,7 +528,7 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
     };
     auto next_valid = [&](uint32_t o, uint32_t j, uint32_t end) -> uint32_t {  // first valid window of read o in
         for (uint32_t b = j; b < end; b += 64u) {                             // [j, end), else end
-            const uint64_t v = vbits(o, b);
+            const uint64_t v = vbits(own_t{}, o, b);  // (phase 1 searches the lane's own bits, below window end)
             if (v) return min(b + (uint32_t)__builtin_ctzll(v), end);
         }
         return end;
@@ -675,7 +710,7 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                             __attribute__((always_inline)) -> bool {  // (x: windows lo + i
         if (hi + 1u <= lo) return true;                                                    // proven absent)
         const uint32_t span = hi + 1u - lo;
-        uint64_t dm0 = vbits(lane, lo) & ~x0, dm1 = span > 64u ? (vbits(lane, lo + 64u) & ~x1) : 0ull;
+        uint64_t dm0 = vbits(own_t{}, lane, lo) & ~x0, dm1 = span > 64u ? (vbits(own_t{}, lane, lo + 64u) & ~x1) : 0ull;
         dm0 &= span >= 64u ? ~0ull : ((1ull << span) - 1ull);
         if (span > 64u) dm1 &= span - 64u >= 64u ? ~0ull : ((1ull << (span - 64u)) - 1ull);
         const uint32_t cnt = (uint32_t)__popcll(dm0) + (uint32_t)__popcll(dm1);
@@ -794,14 +829,19 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
     };
     // a staged lane's piece becomes workable: its valid-window bits (from the bad-base bits the decode left in its
     // valid-window words), T, and phase-1 state (the slots' code words were fenced after the decode)
-    auto finish_piece = [&](uint32_t nch) {
-        // this lane's good-base bits, 16 per chunk from a16 (chunks past its piece are bad), as 8 dwords
-        uint32_t ok[8];
+    // ND: the dwords it works on, a compile-time count (a run-time count over one body spills): 8, or
+    // (LEAN) 6 when no piece of the group has more than AX_FP_NCH6 chunks: the bits from 32 ND on are then bad in every
+    // lane, the dwords that hold them would stay zero through the doubling, and the valid-window words past the
+    // computed ones are stored as zero (the previous piece's bits lie there)
+    auto finish_piece = [&](auto nd_const, uint32_t nch) __attribute__((always_inline)) {
+        constexpr uint32_t ND = decltype(nd_const)::value;
+        // this lane's good-base bits, 16 per chunk from a16 (chunks past its piece are bad), as ND dwords
+        uint32_t ok[ND];
         {
             const uint32_t* vw32 = reinterpret_cast<const uint32_t*>(vw);
             const uint32_t nb = 16u * nch;
 #pragma unroll
-            for (uint32_t d = 0; d < 8u; ++d) {
+            for (uint32_t d = 0; d < ND; ++d) {
                 const uint32_t b0 = 32u * d;  // dword d: chunks 2d, 2d + 1 (word d / 2 of the lane's column)
                 uint32_t v = vw32[((d >> 1) * 64u + lane) * 2u + (d & 1u)];
                 v |= nb <= b0 ? ~0u : (nb < b0 + 32u ? ~0u << (nb - b0) : 0u);
@@ -815,14 +855,14 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
             const uint32_t dw = sft >> 5, bs = sft & 31u;
             if (dw == 0u) {
 #pragma unroll
-                for (uint32_t d = 0; d < 8u; ++d) ok[d] &= alignbit(d + 1u < 8u ? ok[d + 1] : 0u, ok[d], bs);
+                for (uint32_t d = 0; d < ND; ++d) ok[d] &= alignbit(d + 1u < ND ? ok[d + 1] : 0u, ok[d], bs);
             } else if (dw == 1u) {
 #pragma unroll
-                for (uint32_t d = 0; d < 8u; ++d)
-                    ok[d] &= alignbit(d + 2u < 8u ? ok[d + 2] : 0u, d + 1u < 8u ? ok[d + 1] : 0u, bs);
+                for (uint32_t d = 0; d < ND; ++d)
+                    ok[d] &= alignbit(d + 2u < ND ? ok[d + 2] : 0u, d + 1u < ND ? ok[d + 1] : 0u, bs);
             } else {  // sft == 64
 #pragma unroll
-                for (uint32_t d = 0; d < 8u; ++d) ok[d] &= d + 2u < 8u ? ok[d + 2] : 0u;
+                for (uint32_t d = 0; d < ND; ++d) ok[d] &= d + 2u < ND ? ok[d + 2] : 0u;
             }
             len += sft;
         }
@@ -833,10 +873,13 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
             uint32_t tc = 0;  // T (fm_scanner.cpp:164): the piece's passing windows
 #pragma unroll
             for (uint32_t d = 0; d < 2u * AX_VWW; ++d) {
-                uint32_t v = alignbit(d + 1u < 8u ? ok[d + 1] : 0u, ok[d], off0);
-                const uint32_t bit0 = 32u * d;
-                v = wend <= bit0 ? 0u : (wend < bit0 + 32u ? v & ((1u << (wend - bit0)) - 1u) : v);
-                tc += (uint32_t)__popc(v);
+                uint32_t v = 0u;
+                if (d < ND) {
+                    v = alignbit(d + 1u < ND ? ok[d + 1] : 0u, ok[d], off0);
+                    const uint32_t bit0 = 32u * d;
+                    v = wend <= bit0 ? 0u : (wend < bit0 + 32u ? v & ((1u << (wend - bit0)) - 1u) : v);
+                    tc += (uint32_t)__popc(v);
+                }
                 vw32[((d >> 1) * 64u + lane) * 2u + (d & 1u)] = v;
             }
             if (tc) atomicAdd(&wsum[0], (unsigned long long)tc);
@@ -887,7 +930,7 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
 #pragma unroll
                 for (uint32_t t = 0; t < AX_F; ++t) {
                     uint64_t ra[HW];
-                    read_words(ent[t] & 63u, so[t], ra);
+                    read_words(other_t{}, ent[t] & 63u, so[t], ra);
                     hh[t] = ax_hash<HW>(ra, k);
                 }
 #pragma unroll
@@ -921,7 +964,7 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                 // local mode: the first base of lane o's piece (every lane active here: a full-wave shuffle)
                 const uint64_t tao = MODE == KM_LOCAL ? (uint64_t)__shfl((long long)ta, (int)o) : 0ull;
                 uint64_t ra[HW];
-                read_words(o, so, ra);
+                read_words(other_t{}, o, so, ra);
                 const uint64_t h = ax_hash<HW>(ra, k);
                 const uint32_t fp = ax_fp(h);
                 uint32_t b = act ? ax_bucket(h, A.nb) : 0u, sl = 0, pp = 0, pg = 0;
@@ -1018,7 +1061,10 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                 // issue priority by the share of the pool still to do: the SIMD's arbiter favours the oldest wave at
                 // equal priority, so without this the waves dispatched first finish in a third of the time of the
                 // last ones and the SIMD runs the end of the launch with few waves (profiles/r04/stats_gen.jsonl)
-                const uint32_t q = (uint32_t)(((cur_end - cur) * 4u) / (pool_n + 1u));
+                // q = floor(4 rest / (pool_n + 1)) in 0 .. 3, by three compares (the 64-bit scalar division cost about
+                // 140 instructions per refill)
+                const uint64_t r4 = (cur_end - cur) * 4u, n1 = pool_n + 1u;
+                const uint32_t q = (r4 >= n1 ? 1u : 0u) + (r4 >= 2u * n1 ? 1u : 0u) + (r4 >= 3u * n1 ? 1u : 0u);
                 if (q >= 3u) __builtin_amdgcn_s_setprio(3);
                 else if (q == 2u) __builtin_amdgcn_s_setprio(2);
                 else if (q == 1u) __builtin_amdgcn_s_setprio(1);
@@ -1097,7 +1143,15 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
             if (STATS) s_slots += lane == 0 ? SU * full + ns : 0u;
             wave_sync();
             if (STATS) c_rstg += clock64() - c_b;
-            if (stg) finish_piece(nch);
+            // (LEAN) a uniform branch between the two compile-time sizes: 150-bp pieces with their alignment slack have
+            // at most 11 chunks, 176 bits
+            constexpr uint32_t AX_FP_NCH6 = 11u;
+            static_assert(16u * AX_FP_NCH6 <= 32u * 6u && 6u <= 2u * AX_VWW, "six dwords hold AX_FP_NCH6 chunks' bits");
+            if (AX_LEAN_PIECE && __ballot(nch > AX_FP_NCH6) == 0) {
+                if (stg) finish_piece(std::integral_constant<uint32_t, 6u>{}, nch);
+            } else {
+                if (stg) finish_piece(std::integral_constant<uint32_t, 8u>{}, nch);
+            }
             // the slots' code words were fenced after the decode (phase 2 reads other lanes' slots); the valid-window
             // bits are read by their own lane only
             if (STATS) c_ref += clock64() - c_s;
@@ -1131,12 +1185,12 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
         uint64_t ra[HW];
         if (!run_phase && st == 0u) {
             const uint32_t j0 = j;
-            if (SPEC_RW) read_words(lane, off0 + j0, ra);
+            if (SPEC_RW) read_words(own_t{}, lane, off0 + j0, ra);
             j = next_valid(lane, j0, wend);
             if (SPEC && sp != 0u && j >= wend && defer_range(sp, min(sp + k - 2u, wend - 1u)))
                 sp = 0;  // no window left to anchor the pending ones (no room: st 3, kept)
             if (j >= wend && st == 0u) st = 2u;
-            else if (SPEC_RW && j != j0) read_words(lane, off0 + j, ra);
+            else if (SPEC_RW && j != j0) read_words(own_t{}, lane, off0 + j, ra);
         }
         const bool lk = st == 0u && !run_phase, rn = st == 1u && run_phase;
         if (STATS) {
@@ -1148,7 +1202,7 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
         }
         if (!run_phase) {
             // ---- lookup: hash window j -> bucket (8 slots {pos, fp | group}); resolve
-            if (!SPEC_RW) read_words(lane, off0 + j, ra);
+            if (!SPEC_RW) read_words(own_t{}, lane, off0 + j, ra);
             const uint64_t h = ax_hash<HW>(ra, k);
             const uint32_t fp = ax_fp(h);
             if (lk && !resume) {
@@ -1185,7 +1239,7 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                         if (t >= np) break;
                         a = j + (t * km) / (np - 1u);
                     }
-                    const uint64_t x[1] = {slot64(lane, off0 + a)};
+                    const uint64_t x[1] = {slot64(own_t{}, lane, off0 + a)};
                     const uint64_t hm = ax_hash<1>(x, A.m);
                     const uint32_t off = A.mf_off + ax_fword(hm, A.nmf) * 8u;
                     mb[t] = 0x80000000u | ((uint32_t)hm & 0x3FFFFu) | (a << 18);
@@ -1256,7 +1310,7 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                     if (STATS) {
                         const uint32_t lo = e1 + 2u - k, sp_n = dend + 1u - lo;  // (dend + 1 >= lo; <= k - 1 windows)
                         if (dend + 1u > lo) {
-                            uint64_t v0 = vbits(lane, lo), v1 = sp_n > 64u ? vbits(lane, lo + 64u) : 0ull;
+                            uint64_t v0 = vbits(other_t{}, lane, lo), v1 = sp_n > 64u ? vbits(other_t{}, lane, lo + 64u) : 0ull;
                             v0 &= sp_n >= 64u ? ~0ull : ((1ull << sp_n) - 1ull);
                             if (sp_n > 64u) v1 &= sp_n - 64u >= 64u ? ~0ull : ((1ull << (sp_n - 64u)) - 1ull);
                             s_spw += (uint32_t)__popcll(v0) + (uint32_t)__popcll(v1);
@@ -1356,12 +1410,14 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                 if (STATS) s_qb += rn ? 1u : 0u;
             }
             // the read's 16-base dwords from slot position off0 + j
-            const uint32_t rpos = off0 + j, rd0 = rpos >> 4, rsh = 2u * (rpos & 15u);
+            // (LEAN: no guard per row: the first row clamped once, the rows past the piece hold the codes of earlier
+            // pieces or the wave's other arrays, and their bases lie at or past cl)
+            const uint32_t rpos = off0 + j, rd0 = LEAN ? min(rpos >> 4, AX_CHUNKS - 1u) : rpos >> 4, rsh = 2u * (rpos & 15u);
             uint32_t rw[AX_CMPW * 2 + 1];
 #pragma unroll
             for (uint32_t i = 0; i <= 2 * AX_CMPW; ++i) {
                 const uint32_t d = rd0 + i;
-                rw[i] = d < AX_CHUNKS ? codes[d * 64u + lane] : 0u;
+                rw[i] = (LEAN || d < AX_CHUNKS) ? codes[d * 64u + lane] : 0u;
             }
             // a run's own windows (chunk c: windows j + 32 c ..); with varying qualities (local mode), weighed by
             // the whole wave after the run (wl_pend; run group wl_g, first window wl_j)
@@ -1372,21 +1428,30 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
             if (rn) {
                 const uint32_t s5 = p & 31u, q16 = s5 >> 4, tsh = 2u * (s5 & 15u);
                 uint32_t e = cl;  // first mismatching base (cl: none)
+                if constexpr (AX_LEAN_MISMATCH) {  // one pass without a compare and a select per dword (ax_phase1.hpp)
+                    static_assert(2u * AX_CMPW == AXP_CMPD && 2u * AX_NGR == AXP_CMPD + 2u, "ax_phase1.hpp's run geometry");
+                    uint32_t td[2 * AX_NGR];
 #pragma unroll
-                for (int i = 2 * (int)AX_CMPW - 1; i >= 0; --i) {
-                    // text dwords T[m] = gr[m / 2][m % 2]; aligned: bases 16 i .. 16 i + 15 from p
-                    const uint32_t m0 = (uint32_t)i, m1 = (uint32_t)i + 1u, m2 = (uint32_t)i + 2u;
-                    const uint32_t t0 = gr[m0 / 2][m0 % 2], t1 = gr[m1 / 2][m1 % 2];
-                    const uint32_t t2 = m2 / 2 < AX_NGR ? gr[(m2 / 2) % AX_NGR][m2 % 2] : 0u;
-                    const uint32_t tlo = q16 ? t1 : t0, thi = q16 ? t2 : t1;
-                    const uint32_t td = alignbit(thi, tlo, tsh);
-                    const uint32_t rdw = alignbit(rw[i + 1], rw[i], rsh);
-                    uint32_t x = td ^ rdw;
-                    const uint32_t b0 = 16u * (uint32_t)i;
-                    e = x ? b0 + ((uint32_t)__builtin_ctz(x) >> 1) : e;
+                    for (uint32_t m = 0; m < 2u * AX_NGR; ++m) td[m] = gr[m / 2u][m % 2u];
+                    e = axp_first_mismatch(td, rw, s5, rsh, cl);
+                } else {
+#pragma unroll
+                    for (int i = 2 * (int)AX_CMPW - 1; i >= 0; --i) {
+                        // text dwords T[m] = gr[m / 2][m % 2]; aligned: bases 16 i .. 16 i + 15 from p
+                        const uint32_t m0 = (uint32_t)i, m1 = (uint32_t)i + 1u, m2 = (uint32_t)i + 2u;
+                        const uint32_t t0 = gr[m0 / 2][m0 % 2], t1 = gr[m1 / 2][m1 % 2];
+                        const uint32_t t2 = m2 / 2 < AX_NGR ? gr[(m2 / 2) % AX_NGR][m2 % 2] : 0u;
+                        const uint32_t tlo = q16 ? t1 : t0, thi = q16 ? t2 : t1;
+                        const uint32_t td = alignbit(thi, tlo, tsh);
+                        const uint32_t rdw = alignbit(rw[i + 1], rw[i], rsh);
+                        uint32_t x = td ^ rdw;
+                        const uint32_t b0 = 16u * (uint32_t)i;
+                        e = x ? b0 + ((uint32_t)__builtin_ctz(x) >> 1) : e;
+                    }
                 }
-                // bases past cl compare whatever lies there (zeros past the staged chunks and the loaded
-                // granules): a mismatch among them only matters as "none before cl"
+                // bases past cl compare whatever lies there (the codes of earlier pieces, the wave's other arrays
+                // or, guarded, zeros past the staged chunks; zeros past the loaded granules): a mismatch among them
+                // only matters as "none before cl"
                 e = min(e, cl);
                 // (SPEC) a speculative run must stay in its anchor's text: an END window (a text end) among the pending
                 // windows [0, pb) defers them, and the anchored window is compared from its own position next
@@ -1447,7 +1512,7 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                     uint32_t nback = 0;  // (STATS) the valid windows of [lo, hi]: no longer dropped
                     if (STATS && mism && e + 1u < k && hi + 1u > lo) {
                         const uint32_t sp_n = hi + 1u - lo;
-                        uint64_t v0 = vbits(lane, lo), v1 = sp_n > 64u ? vbits(lane, lo + 64u) : 0ull;
+                        uint64_t v0 = vbits(other_t{}, lane, lo), v1 = sp_n > 64u ? vbits(other_t{}, lane, lo + 64u) : 0ull;
                         v0 &= sp_n >= 64u ? ~0ull : ((1ull << sp_n) - 1ull);
                         if (sp_n > 64u) v1 &= sp_n - 64u >= 64u ? ~0ull : ((1ull << (sp_n - 64u)) - 1ull);
                         nback = (uint32_t)__popcll(v0) + (uint32_t)__popcll(v1);
@@ -1470,7 +1535,7 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                         // deferred-window pass and then takes the lookup path (verify unset)
                         if (STATS) {
                             const uint32_t l0 = j + 1u - k, h0 = min(j, wend) - 1u, n0 = h0 + 1u - l0;
-                            uint64_t v0 = vbits(lane, l0), v1 = n0 > 64u ? vbits(lane, l0 + 64u) : 0ull;
+                            uint64_t v0 = vbits(other_t{}, lane, l0), v1 = n0 > 64u ? vbits(other_t{}, lane, l0 + 64u) : 0ull;
                             v0 &= n0 >= 64u ? ~0ull : ((1ull << n0) - 1ull);
                             if (n0 > 64u) v1 &= n0 - 64u >= 64u ? ~0ull : ((1ull << (n0 - 64u)) - 1ull);
                             s_spw -= (uint32_t)__popcll(v0) + (uint32_t)__popcll(v1);
@@ -1497,12 +1562,13 @@ __global__ __launch_bounds__(AX_THREADS, (ax_min_waves<MODE, HW, EM, STATS>())) 
                     uint32_t vm[AX_CMPW];
                     {
                         const uint32_t* vw32 = reinterpret_cast<const uint32_t*>(vw);
-                        const uint32_t d = j >> 5, vs = j & 31u;
+                        // (LEAN: no guard per dword: every bit past R is masked by run_mask)
+                        const uint32_t d = LEAN ? min(j >> 5, (AX_CAP - 1u) / 32u) : j >> 5, vs = j & 31u;
                         uint32_t vd[AX_CMPW + 1];
 #pragma unroll
                         for (uint32_t i = 0; i <= AX_CMPW; ++i) {
                             const uint32_t di = d + i;
-                            vd[i] = di < 2u * AX_VWW ? vw32[((di >> 1) * 64u + lane) * 2u + (di & 1u)] : 0u;
+                            vd[i] = (LEAN || di < 2u * AX_VWW) ? vw32[((di >> 1) * 64u + lane) * 2u + (di & 1u)] : 0u;
                         }
 #pragma unroll
                         for (uint32_t i = 0; i < AX_CMPW; ++i) vm[i] = alignbit(vd[i + 1], vd[i], vs);
