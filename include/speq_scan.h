@@ -697,6 +697,18 @@ int speq_device_prepare(speq_device_index* d, uint32_t k, uint64_t* distinct_kme
  * SPEQ_E_ARG when the anchor-and-extend scan does not take k. Blocking. */
 int speq_device_sproof_bitmap(speq_device_index* d, uint32_t k, uint64_t* words, uint64_t n_words);
 
+/* Test accessor: what replica d holds for k, building nothing. facts (host, u64[n_facts], n_facts >=
+ * SPEQ_BUILD_FACTS): [0] the anchor structures of k: 0 not asked for yet, 1 built, 2 deferred because the free device
+ * memory was short (the next scan tries again), 3 refused (k, the group count or a 32-bit buffer offset: never
+ * retried); of a built table [1] buckets nb, [2] filter words nf, [3] m of the m-mer filter (0: none), [4] its words
+ * nmf, [5] the substitution bitmap's byte offset s_off, [6] its words s_words (0: none), [7] 1 when the representatives
+ * came from the suffix sort, [8] 1 when the EM-only arrays exist, [9] the distinct k-mers; [10] the plane families the
+ * replica published (bit 0 one-symbol, bit 1 two-symbol, bit 2 three-symbol); [11] the k-mer table of k: 0 not asked
+ * for yet, 1 wide, 2 compact, 3 none (too large for the free memory at the time: kept for the replica's life); [12]
+ * text positions n, [13] texts. */
+#define SPEQ_BUILD_FACTS 14
+int speq_device_build_facts(speq_device_index* d, uint32_t k, uint64_t* facts, uint32_t n_facts);
+
 /* Test accessor: one run of the GPU FASTQ parser (fastq_gpu.hip, the parser of speq_scan_fastq's raw blocks) on
  * `device`. raw (host) holds file 1's four-line text [0, len1) followed, when paired, by file 2's [len1, len1 + len2);
  * n_records is the record count per file. The text is copied into a 16-byte aligned device buffer of

@@ -213,10 +213,20 @@ SIGNATURES = {
     "speq_device_get_tuning": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
     "speq_device_prepare": (C.c_int, [_P, C.c_uint32, _U64P, _U64P, _F64P]),
     "speq_device_sproof_bitmap": (C.c_int, [_P, C.c_uint32, _U64P, C.c_uint64]),
+    "speq_device_build_facts": (C.c_int, [_P, C.c_uint32, _U64P, C.c_uint32]),
     "speq_fastq_parse_block": (C.c_int, [C.c_int, _P, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint8,
                                          C.c_uint8, _P, _P, _U64P, C.POINTER(C.c_uint32), _U64P]),
     "speq_timing_enable": (C.c_int, [_P, C.c_int]),
     "speq_timing_read": (C.c_int, [_P, _F64P, _U64P]),
+}
+
+# test seams of dev_mem.cpp: exported, not part of include/speq_scan.h
+DEBUG_SIGNATURES = {
+    "speq_debug_allocs": (None, [_U64P, _U64P]),
+    "speq_debug_fail_alloc": (None, [C.c_int64]),
+    "speq_debug_free_queries": (None, [_U64P]),
+    "speq_debug_free_bytes": (None, [C.c_int64, C.c_uint64]),
+    "speq_debug_offset_limit": (None, [C.c_uint64]),
 }
 
 _lib = None
@@ -234,7 +244,7 @@ def lib() -> C.CDLL:
             raise ImportError(f"{LIB_PATH} is missing: build it with `make` (or __graft_entry__.build()); "
                               "the SPeQ scan path has no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **DEBUG_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

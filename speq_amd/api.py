@@ -28,6 +28,30 @@ __all__ = ["FmIndex", "DeviceIndex", "Node", "Pipeline", "ScanResult", "ReadRepo
            "em_refine", "pack_records", "SpeqError", "SPEQ_MODE_GLOBAL", "SPEQ_MODE_LOCAL"]
 
 
+def debug_allocs() -> tuple[int, int]:
+    """Test seam (dev_mem.cpp): device allocations of the library (alive now, made since the process started)."""
+    live, made = C.c_uint64(), C.c_uint64()
+    lib().speq_debug_allocs(C.byref(live), C.byref(made))
+    return live.value, made.value
+
+
+def debug_free_queries() -> int:
+    """Test seam: free-memory queries the library has made since the process started."""
+    made = C.c_uint64()
+    lib().speq_debug_free_queries(C.byref(made))
+    return made.value
+
+
+def debug_free_bytes(nth: int, nbytes: int = 0) -> None:
+    """Test seam: the nth free-memory query from now answers min(real, nbytes); one-shot, nth 0 disarms."""
+    lib().speq_debug_free_bytes(nth, nbytes)
+
+
+def debug_offset_limit(limit: int = 0) -> None:
+    """Test seam: the host's offset decisions take `limit` for 2^32 until it is set again; 0 restores 2^32."""
+    lib().speq_debug_offset_limit(limit)
+
+
 def _u64p(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_uint64))
 
@@ -551,6 +575,17 @@ class DeviceIndex:
         words = np.zeros((n + 63) // 64, dtype=np.uint64)
         check(lib().speq_device_sproof_bitmap(self._h, k, _u64p(words), len(words)))
         return np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
+
+    BUILD_FACTS = ("ax", "nb", "nf", "m", "nmf", "s_off", "s_words", "sa_reps", "em_arrays", "distinct", "planes",
+                   "ktab", "n", "n_texts")
+
+    def build_facts(self, k: int) -> dict:
+        """Test accessor (speq_device_build_facts): what the replica holds for k, building nothing. "ax": 0 not asked
+        for, 1 built, 2 deferred (free memory was short), 3 refused; "planes": bit 0 / 1 / 2 the one- / two- /
+        three-symbol planes it published; "ktab": 0 not asked for, 1 wide, 2 compact, 3 none."""
+        f = np.zeros(len(self.BUILD_FACTS), dtype=np.uint64)
+        check(lib().speq_device_build_facts(self._h, k, _u64p(f), len(f)))
+        return {name: int(x) for name, x in zip(self.BUILD_FACTS, f)}
 
     def timing(self, on: bool) -> None:
         check(lib().speq_timing_enable(self._h, int(on)))

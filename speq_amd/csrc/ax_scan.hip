@@ -44,6 +44,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "build_limits.hpp"
 #include "device_index.hpp"
 #include "fm_index.hpp"
 #include "scan_device.hpp"
@@ -343,11 +344,7 @@ __global__ void k_ax_sbitmap(const uint64_t* __restrict__ t2, const uint64_t* __
 // round trip, which the deferred windows it saves repay from about 12 on (config 2, k = 21, m = 14: 8 windows per
 // probe, 1-3 % slower with the proofs; k = 31, m = 16-18 and k = 70 win: profiles/r05/ab_mproof*.jsonl); 0 = none
 constexpr uint32_t AX_MP_COVER = 12;
-static uint32_t ax_mproof_m(uint64_t n, uint32_t k) {
-    uint32_t m = 12;
-    while (m < 32u && (double)(1ull << (2u * m)) < 200.0 * (double)n) ++m;
-    return k + 1u >= m + AX_MP_COVER ? m : 0u;
-}
+static uint32_t ax_mproof_m(uint64_t n, uint32_t k) { return speq::limits::ax_mfilter_m(n, k, AX_MP_COVER); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // The scan
@@ -1855,15 +1852,13 @@ AxTable build_ax(speq_device_index* d, uint32_t k) {
     AxTable ax;
     const uint64_t n = d->view.n;
     if (k < 1 || k > AX_MAX_K || n >= (1ull << 30) || d->G > AX_MAX_G) return ax;
-    const uint64_t nw64 = (n + 63) / 64 + 4;
-    const uint64_t n_gran = (n + 255) / 32 + 2;  // a run from any p < n reads <= AX_NGR granules: padded with END
-    const uint64_t gran_bytes = n_gran * 16;
-    size_t free_b = 0, total_b = 0;
-    HIP_OK(hipMemGetInfo(&free_b, &total_b));
-    // gran, codes, owner, text2 + tbad, table + filter (bounds); the EM-only mlo / mhi come later (ensure_ax_em)
-    const uint64_t need = gran_bytes + n + (n + 64) * 4 + nw64 * 24 + n * 12;
-    if (need > free_b / 10 * 9) {
+    // (n_gran: a run from any p < n reads <= AX_NGR granules: padded with END; need: gran, codes, owner, text2 +
+    // tbad, table + filter (bounds); the EM-only mlo / mhi come later, ensure_ax_em)
+    const limits::AxNeed need = limits::ax_need(n);
+    const uint64_t nw64 = need.nw64, n_gran = need.n_gran, gran_bytes = need.gran_bytes;
+    if (!limits::ax_build_fits(need, mem::free_bytes())) {
         ax.transient = true;
+        startup_trace("per-k structures deferred: free device memory is short");
         return ax;
     }
     const char* who = "build_ax";
@@ -1883,8 +1878,7 @@ AxTable build_ax(speq_device_index* d, uint32_t k) {
         d->d_tbad = d->adopt(std::move(tbad));
         d->d_text2 = d->adopt(std::move(text2));
     }
-    HIP_OK(hipMemGetInfo(&free_b, &total_b));
-    if (n * 60 + need < free_b / 10 * 9) {
+    if (limits::ax_sort_fits(n, need, mem::free_bytes())) {
         sa = DevPtr<uint32_t>::alloc(n, who);
         try {
             HIP_OK(hipStreamSynchronize(d->stream));
@@ -1916,30 +1910,30 @@ AxTable build_ax(speq_device_index* d, uint32_t k) {
     unsigned long long distinct = 0;
     HIP_OK(hipMemcpyAsync(&distinct, d_cnt.get(), 8, hipMemcpyDeviceToHost, d->stream));
     HIP_OK(hipStreamSynchronize(d->stream));
+    const bool sa_reps = (bool)sa;
     sa.reset();  // read by k_ax_classify only
-    ax.distinct = distinct;
     const uint32_t load = ax_effective_load(d);
-    ax.nf = std::max<uint64_t>(1, distinct * AX_FILTER_BITS / 64);
-    ax.nb = std::max<uint64_t>(1, (uint64_t)((double)distinct * 100.0 / (8.0 * load)) + 1);
     // the m-mer filter (k_ax_mfilter) after the buckets: 16 bits per m-mer, sized by the distinct k-mers plus
     // the m-mers that start no valid k-mer window near a text end (k per text); an undersized filter only
     // passes more m-mers (their windows are deferred as before), it never proves a present window absent
-    ax.m = ax_mproof_m(n, k);
-    ax.nmf = ax.m ? std::max<uint64_t>(1, (distinct + (uint64_t)d->n_texts * k) * AX_FILTER_BITS / 64) : 0;
-    if (ax.m && ax.nb * 64u + ax.nmf * 8u + 16u >= (1ull << 32) - 64) ax.m = 0, ax.nmf = 0;
-    // the scan addresses the tables with 32-bit buffer offsets: leave this k to the other kernels
-    if (ax.nb * 64u >= (1ull << 32) - 64 || ax.nf * 8 >= (1ull << 32) - 64) return AxTable{};
-    // the substitution bitmap S (k_ax_sbitmap, filled by ensure_ax_sproof) after the m-mer filter: 1 bit per text
+    // the scan addresses the tables with 32-bit buffer offsets (limits::ax_layout): beyond them the m-mer filter
+    // goes first, then the table is refused (leave this k to the other kernels), and the bitmap has no room.
+    // The substitution bitmap S (k_ax_sbitmap, filled by ensure_ax_sproof) after the m-mer filter: 1 bit per text
     // position in whole blocks of 256, + 16 B of load slack; all zero (no proofs) until it is filled
-    ax.s_off = ax.nb * 64u + (ax.m ? ax.nmf * 8u + 16u : 0u);
-    ax.s_words = SPEQ_AX_SPROOF ? ((n + 255) / 256) * 4 : 0;
-    if (ax.s_off + ax.s_words * 8u + 16u >= (1ull << 32) - 64) ax.s_words = 0;
-    const uint64_t s_bytes = ax.s_words ? ax.s_words * 8u + 16u : 0u;
-    HIP_OK(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t atab_bytes = ax.s_off + s_bytes;
-    if (atab_bytes + ax.nf * 8 > free_b / 10 * 9) {  // the table and filters do not fit now: try again later
+    const limits::AxLayout lay = limits::ax_layout(n, k, distinct, d->n_texts, load, AX_FILTER_BITS, ax_mproof_m(n, k),
+                                                   SPEQ_AX_SPROOF != 0, mem::offset_limit());
+    if (lay.refused) {
+        startup_trace("per-k structures refused: beyond 32-bit buffer offsets");
+        return AxTable{};
+    }
+    ax.distinct = distinct;
+    ax.sa_reps = sa_reps;
+    ax.nf = lay.nf, ax.nb = lay.nb, ax.m = lay.m, ax.nmf = lay.nmf, ax.s_off = lay.s_off, ax.s_words = lay.s_words;
+    const uint64_t s_bytes = lay.s_bytes, atab_bytes = lay.atab_bytes;
+    if (!limits::ax_table_fits(lay, mem::free_bytes())) {  // the table and filters do not fit now: try again later
         AxTable t;
         t.transient = true;
+        startup_trace("per-k structures deferred: free device memory is short");
         return t;
     }
     filt = DevPtr<>::alloc(ax.nf * 8, who);
@@ -1991,9 +1985,7 @@ static bool ensure_ax_em(speq_device_index* d, AxTable* ax, uint32_t k) {
     if (ax->mlo) return true;
     DeviceGuard g(d->device);
     const uint64_t n = d->view.n;
-    size_t free_b = 0, total_b = 0;
-    HIP_OK(hipMemGetInfo(&free_b, &total_b));
-    if ((n + 64) * 8 > free_b / 10 * 9) return false;
+    if (!limits::ax_em_fits(n, mem::free_bytes())) return false;
     DevPtr<uint32_t> mlo = DevPtr<uint32_t>::alloc(n + 64, "ensure_ax_em");
     DevPtr<uint32_t> mhi = DevPtr<uint32_t>::alloc(n + 64, "ensure_ax_em");
     SyncOnExit sync(d->stream);
@@ -2006,7 +1998,7 @@ static bool ensure_ax_em(speq_device_index* d, AxTable* ax, uint32_t k) {
     d->allocs.reserve(d->allocs.size() + 2);
     ax->mhi = d->adopt(std::move(mhi));
     ax->mlo = d->adopt(std::move(mlo));  // last: the unlocked check in ax_facts reads it
-    ax->bytes += (n + 64) * 8;
+    ax->bytes += limits::ax_em_bytes(n);
     return true;
 }
 

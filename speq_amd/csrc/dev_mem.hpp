@@ -23,6 +23,11 @@ namespace mem {
 // bytes)") when it does not fit, speq::DeviceError for any other failure.
 void* raw_alloc(size_t bytes, const char* who);
 void raw_free(void* p) noexcept;  // null: nothing
+// Free bytes of the current device: the library's only question of this kind (build_limits.hpp decides from the
+// answer). Throws speq::DeviceError when the device does not answer.
+uint64_t free_bytes();
+// The span of a 32-bit buffer offset, 2^32, as build_limits.hpp's offset decisions take it (host side only).
+uint64_t offset_limit();
 }  // namespace mem
 
 // Move-only owner of one device allocation; frees it when it goes. T = void counts in bytes.
@@ -88,4 +93,12 @@ extern "C" {
 void speq_debug_allocs(uint64_t* live, uint64_t* made);
 // The nth allocation from now throws OutOfDeviceMemory before the device is asked; one-shot, 0 disarms.
 void speq_debug_fail_alloc(int64_t nth);
+// made: free-memory queries (mem::free_bytes) since the process started.
+void speq_debug_free_queries(uint64_t* made);
+// The nth free-memory query from now answers min(real, bytes): the library believes memory is short, none is taken.
+// One-shot, nth 0 disarms.
+void speq_debug_free_bytes(int64_t nth, uint64_t bytes);
+// mem::offset_limit() answers `limit` (clamped to [4096, 2^32]) until it is set again; 0 restores 2^32. What was
+// decided under a limit (a refused table, an unpublished plane family) stays decided.
+void speq_debug_offset_limit(uint64_t limit);
 }

@@ -41,6 +41,7 @@ struct AxTable {
     double build_ms = 0.0;
     bool ok = false;
     bool transient = false;    // !ok only because the free HBM was short at build time (ensure_ax retries)
+    bool sa_reps = false;      // the representatives are the medians of the suffix-array intervals (else first claimants)
 };
 }  // namespace speq
 

@@ -34,6 +34,7 @@
 #include <string>
 #include <vector>
 
+#include "build_limits.hpp"
 #include "capi_internal.hpp"
 #include "em.hpp"
 #include "scan_internal.hpp"
@@ -1274,11 +1275,7 @@ DevView scan_view(const speq_device_index* d, uint32_t k) {
     return v;
 }
 
-uint64_t next_pow2(uint64_t x) {
-    uint64_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
+using speq::limits::next_pow2;
 
 // Builds the k-mer interval table of k on the replica's stream (blocking): the distinct N-free k-mers of the texts
 // (k_ktab_keys into a set of 2x the window count), then one FM-index search per distinct k-mer (k_ktab_fill) into
@@ -1297,13 +1294,13 @@ speq_device_index::KmerTable build_ktab(speq_device_index* d, uint32_t k) {
     DevPtr<unsigned long long> keys, d_cnt;
     DevPtr<uint64_t> d_cum;
     unsigned long long distinct = 0;
-    const uint64_t slots = next_pow2(std::max<uint64_t>(2 * total, 64));
     // too large for 32-bit bucket hashing, or for the free HBM (key set + a table of up to 4 slots per window):
     // no table, scans of this k use LF steps (same results)
-    size_t free_b = 0, total_b = 0;
-    HIP_OK(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t need = slots * 8 + next_pow2(std::max<uint64_t>(1, total * d->kt_slots / KT_BSLOTS)) * 16 * KT_BSLOTS;
-    if (slots > (1ull << 32) || need > free_b / 10 * 9) return kt;  // kt.table == nullptr
+    const speq::limits::KtNeed need = speq::limits::kt_need(total, d->n_texts, d->kt_slots, KT_BSLOTS);
+    const uint64_t slots = need.slots;
+    // (limit: 2^32; a test that lowers it for build_ax's offsets lowers it for the slot and bucket counts here too)
+    const uint64_t free_b = mem::free_bytes(), limit = mem::offset_limit();
+    if (!speq::limits::kt_build_fits(need, free_b, limit)) return kt;  // kt.table == nullptr
     SyncOnExit sync(d->stream);  // after the buffers above, and every later one lives in a scope inside its own
     if (total > 0) {
         keys = DevPtr<unsigned long long>::alloc(slots, who);
@@ -1323,14 +1320,14 @@ speq_device_index::KmerTable build_ktab(speq_device_index* d, uint32_t k) {
     kt.distinct = distinct;
     // compact form first (k <= KT8_MAX_K): sized for the load factor kt_load8; if the multi-group k-mers outgrow the
     // payload bits, fall through to the 16-B-slot form
-    const uint32_t pbits = 64u - 2u * k;
-    const uint64_t multi_cap = std::min<uint64_t>(distinct, (1ull << (pbits - 1u)) - 2u);
-    const uint64_t nb8 = std::max<uint64_t>(1, (uint64_t)((double)distinct * 100.0 / (8.0 * d->kt_load8)) + 1);
     // the fill writes the multi-group k-mers into a scratch array of the worst-case size (every distinct k-mer),
     // copied to one of the exact size afterwards; the free-memory check covers the scratch
-    const bool try_compact = d->kt_compact && KT_BSLOTS == 4 && k <= KT8_MAX_K && distinct > 0 && nb8 < (1ull << 32);
-    if (try_compact && nb8 * 64 + std::max<uint64_t>(multi_cap, 1) * 8 > free_b / 10 * 9)
-        return kt;  // kt.table == nullptr: LF steps
+    const bool compact_k = d->kt_compact && KT_BSLOTS == 4 && k <= KT8_MAX_K && distinct > 0;
+    const speq::limits::KtCompact cpt = compact_k ? speq::limits::kt_compact(distinct, k, d->kt_load8, limit)
+                                                  : speq::limits::KtCompact{};
+    const uint64_t multi_cap = cpt.multi_cap, nb8 = cpt.nb8;
+    const bool try_compact = compact_k && cpt.addressable;
+    if (try_compact && !speq::limits::kt_compact_fits(need, cpt, free_b)) return kt;  // kt.table == nullptr: LF steps
     if (try_compact) {
         DevPtr<unsigned long long> tab = DevPtr<unsigned long long>::alloc(nb8 * 8, who);
         DevPtr<uint2> multi = DevPtr<uint2>::alloc(std::max<uint64_t>(multi_cap, 1), who);
@@ -1362,7 +1359,7 @@ speq_device_index::KmerTable build_ktab(speq_device_index* d, uint32_t k) {
             return kt;
         }
     }
-    kt.buckets = next_pow2(std::max<uint64_t>(1, (distinct * d->kt_slots + KT_BSLOTS - 1) / KT_BSLOTS));
+    kt.buckets = speq::limits::kt_wide_buckets(distinct, d->kt_slots, KT_BSLOTS);
     kt.bytes = kt.buckets * 16 * KT_BSLOTS;
     DevPtr<uint4> wide = DevPtr<uint4>::alloc(kt.buckets * KT_BSLOTS, who);
     SyncOnExit sync_wide(d->stream);
@@ -1608,8 +1605,19 @@ int speq_device_open(const speq_index* idx, int device, speq_device_index** out)
         DevView& v = d->view;
         v.occ = reinterpret_cast<const uint4*>(d->adopt(dev_upload(fm.occ)));
         v.nb = (uint32_t)fm.n_blocks();
-        v.occ2 = reinterpret_cast<const uint4*>(d->adopt(dev_upload(fm.occ2)));
-        v.occ3 = reinterpret_cast<const uint4*>(d->adopt(dev_upload(fm.occ3)));
+        // the searches address a plane family with 32-bit offsets: a family too large for them (the three-symbol
+        // planes from n = 402,653,088, the two-symbol planes from n = 1,610,612,640) is neither uploaded nor
+        // published, and the searches step by fewer symbols with the same results
+        const speq::limits::PlaneFamilies fam =
+            speq::limits::plane_families(fm.n_blocks(), !fm.occ2.empty(), !fm.occ3.empty(), mem::offset_limit());
+        if (!fam.occ) throw std::invalid_argument("speq_device_open: the index is too large for 32-bit plane offsets");
+        if (fam.occ2) v.occ2 = reinterpret_cast<const uint4*>(d->adopt(dev_upload(fm.occ2)));
+        if (fam.occ3) v.occ3 = reinterpret_cast<const uint4*>(d->adopt(dev_upload(fm.occ3)));
+        if (!fm.occ3.empty() && !fam.occ3)
+            speq::startup_trace(fam.occ2 ? "device open: three-symbol planes left out (32-bit plane offsets)"
+                                         : "device open: two- and three-symbol planes left out (32-bit plane offsets)");
+        else if (!fm.occ2.empty() && !fam.occ2)
+            speq::startup_trace("device open: two-symbol planes left out (32-bit plane offsets)");
         v.runs = reinterpret_cast<const uint4*>(d->adopt(dev_upload(fm.runs)));
         v.run_label = d->adopt(dev_upload(fm.run_label));
         v.lab = d->adopt(dev_upload(fm.lab));
@@ -1643,8 +1651,9 @@ int speq_device_open(const speq_index* idx, int device, speq_device_index** out)
         // (fewer concurrent gathers thrashing L1/L2); an L2-resident index wants every wave it can get.
         // (With the two-symbol planes the gather chain is half as long and full occupancy wins again.)
         const uint64_t acgt_bytes = 4ull * fm.n_blocks() * sizeof(speq::OccEntry);
-        d->blocks_per_cu = (fm.occ2.empty() && acgt_bytes > (4ull << 20)) ? 3u : 0u;
-        if (!fm.occ3.empty()) {
+        // (by what was published, not by what the file holds)
+        d->blocks_per_cu = (!fam.occ2 && acgt_bytes > (4ull << 20)) ? 3u : 0u;
+        if (fam.occ3) {
             // With the three-symbol planes (measured, profiles/r01/sweep_grid_triples.jsonl, sweep_bpc_cfg*.jsonl):
             // planes that spill L2 but fit the 256 MB Infinity Cache want 4 blocks/CU (cfg 3: +12 %); planes that
             // spill the Infinity Cache too, so gathers go to HBM, want 3 (cfg 5: 2.1x); small ones want them all.
@@ -2028,6 +2037,32 @@ int speq_device_sproof_bitmap(speq_device_index* d, uint32_t k, uint64_t* words,
         if (n_words < need) throw std::invalid_argument("speq_device_sproof_bitmap: n_words < ceil(n / 64)");
         DeviceGuard g(d->device);
         HIP_OK(hipMemcpy(words, static_cast<const char*>(ax->atab) + ax->s_off, need * 8, hipMemcpyDeviceToHost));
+    });
+}
+
+int speq_device_build_facts(speq_device_index* d, uint32_t k, uint64_t* facts, uint32_t n_facts) {
+    return speq::guarded([&] {
+        if (!d || !facts) throw std::invalid_argument("speq_device_build_facts: null argument");
+        if (n_facts < SPEQ_BUILD_FACTS) throw std::invalid_argument("speq_device_build_facts: n_facts too small");
+        std::fill(facts, facts + n_facts, 0);
+        {
+            std::lock_guard<std::mutex> lk(d->ax_mu);
+            const auto it = d->axtabs.find(k);
+            if (it != d->axtabs.end()) {
+                const speq::AxTable& ax = it->second;
+                facts[0] = ax.ok ? 1u : ax.transient ? 2u : 3u;
+                facts[1] = ax.nb, facts[2] = ax.nf, facts[3] = ax.m, facts[4] = ax.nmf, facts[5] = ax.s_off;
+                facts[6] = ax.s_words, facts[7] = ax.sa_reps ? 1u : 0u, facts[8] = ax.mlo != nullptr ? 1u : 0u;
+                facts[9] = ax.distinct;
+            }
+        }
+        facts[10] = (d->view.occ ? 1u : 0u) | (d->view.occ2 ? 2u : 0u) | (d->view.occ3 ? 4u : 0u);
+        {
+            std::lock_guard<std::mutex> lk(d->kt_mu);
+            const auto it = d->ktabs.find(k);
+            if (it != d->ktabs.end()) facts[11] = !it->second.table ? 3u : it->second.compact ? 2u : 1u;
+        }
+        facts[12] = d->view.n, facts[13] = d->n_texts;
     });
 }
 
